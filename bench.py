@@ -16,12 +16,17 @@ N > 1 GPUs each rank inverts its own 100M-visibility shard of a longer
 observation (weak scaling) and the partial dirty images and weight sums are
 reduced to rank 0 over RCCL (no other collective exists on this path).
 
-Prints ONE JSON line (rank 0). `roofline` is for the dominant kernel (the
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times `--steps`
+steps, writes the last timed step's outputs if `--dump-outputs DIR` is given
+and prints the headline (`value`, `ms_per_step`). Everything else is measured
+only with `--full`: `roofline` is for the dominant kernel (the
 scatter), timed with hipEvents recorded by libcip_hip on the stream it launches
 on; `cpu_baseline` times a tiled fp64 CPU restatement of ducc0's gridder
 (oracle/cpu_baseline.c) on the whole workload (plus C1, C2 and the numpy
 Stokes-I prep); `max_err` is the dirty image's max |GPU - CPU oracle| / sum w
-on a row subset at the full grid (the metric's second half).
+on a row subset at the full grid (the metric's second half); the synchronous
+rate, the phase breakdown, the parity checks and the secondary figures
+(reference call, strong C4) belong there too.
 """
 
 import argparse
@@ -52,6 +57,28 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_PIXELS = 1 << 22  # 32 MiB of float64 per dumped image
+
+
+def dump_outputs(directory, image, sum_weights=None):
+    """`--dump-outputs DIR` (rank 0): what the last timed step handed its
+    caller, as float64 .npy files. `dirty.npy` is the whole image when it has
+    at most DUMP_MAX_PIXELS pixels, else its values at DUMP_MAX_PIXELS flat
+    pixel indices drawn once from a fixed seed (sorted; the same at every run,
+    so two builds' dumps compare element for element); `sum_weights.npy` is the
+    call's weight sum where the path returns one."""
+    import torch
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    if image.numel() > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(20241008).integers(0, image.numel(), DUMP_MAX_PIXELS))
+        image = image.reshape(-1)[torch.from_numpy(idx).to(image.device)]
+    np.save(out / "dirty.npy", image.to(torch.float64).cpu().numpy())
+    if sum_weights is not None:
+        np.save(out / "sum_weights.npy", sum_weights.to(torch.float64).cpu().numpy())
 
 
 def make_raw_columns(cfg, rank, device, seed=20241008):
@@ -320,6 +347,7 @@ def run_strong(args, world, rank, device, steps=None, warmup=None):
         pending[0] = None
         return img_last
 
+    dump = args.dump_outputs if steps is None else None  # the main line's image only, not a secondary's
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     for _ in range(warmup):
@@ -331,20 +359,24 @@ def run_strong(args, world, rank, device, steps=None, warmup=None):
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
-    drain()
+    img = drain()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if dump and rank == 0:
+        dump_outputs(dump, img)
     stages = {}
     nprof = max(2, min(steps, 5))
-    for _ in range(nprof):
+    parity = None
+    for _ in range(nprof if args.full else 0):
         img = step(stages)
     # parity at EVERY rank count, outside the timed region: each rank sums the
     # fp64 DFT of its own visibilities at 8 fixed pixels, the sums are
     # all-reduced and rank 0 compares them with the gathered image
-    parity = strong_parity(data, freq, img, npix, px, world, rank, device)
-    if world == 1 and data.slice_uvw.shape[0] == rows and nvis == rows * nchan:
+    if args.full:
+        parity = strong_parity(data, freq, img, npix, px, world, rank, device)
+    if args.full and world == 1 and data.slice_uvw.shape[0] == rows and nvis == rows * nchan:
         # one strip holding every row whole: the same visibilities as a dense
         # MS - the strip path against the one-shot cip_ms2dirty (fp64 classes,
         # fixed-point quanta of the two calls differ)
@@ -509,17 +541,19 @@ def run_strong_wplanes(args, world, rank, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        img = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
     stages = {}
     nprof = max(2, min(args.steps, 5))
-    for _ in range(nprof):
+    for _ in range(nprof if args.full else 0):
         img = step(stages)
     parity = None
-    if world == 1:
+    if args.full and world == 1:
         ref, _ = gridder_ms2dirty_ref(uvw_d, freq_d, vis_d, wgt_d, npix, px, params.support, args.single)
         parity = {"max_abs_diff_vs_one_shot": float((img - ref).abs().max()), "peak": float(ref.abs().max()),
                   "what": "normalised images: invert_wplanes (1 rank) vs cip_ms2dirty"}
@@ -595,17 +629,19 @@ def run_strong_wstrips(args, world, rank, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        img = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
     stages = {}
     nprof = max(2, min(args.steps, 5))
-    for _ in range(nprof):
+    for _ in range(nprof if args.full else 0):
         img = step(stages)
     parity = None
-    if world == 1:
+    if args.full and world == 1:
         ref, _ = gridder_ms2dirty_ref(uvw_d, freq_d, vis_d, wgt_d, npix, px, params.support, args.single)
         parity = {"max_abs_diff_vs_one_shot": float((img - ref).abs().max()), "peak": float(ref.abs().max()),
                   "what": "normalised images: w-stacking invert_strips (1 strip) vs cip_ms2dirty"}
@@ -702,6 +738,13 @@ def main():
     ap.add_argument("--single", action="store_true",
                     help="packed single-precision accumulation class (CIP_ACC_SINGLE; the precision class of the "
                          "reference's float32 ducc0 call) - secondary measurement, not the f64 metric")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: synchronous rate, phase breakdown and roofline, parity "
+                         "checks, max|err| against the CPU oracle, CPU baseline, secondary figures (the --no-* "
+                         "options below drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (rank 0) to DIR/dirty.npy and "
+                         "DIR/sum_weights.npy (float64; an image of more than 2^22 pixels as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync", action="store_true",
                     help="synchronous steps (diagnostic: per-kernel times without the pipelined overlap)")
@@ -728,6 +771,8 @@ def main():
     ap.add_argument("--no-strong-secondary", action="store_true",
                     help="skip the strong-scaling C4 secondary (secondary.strong_c4) of the default run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `bench.py --gpus N` outside a launcher: start N rank processes (one
@@ -847,40 +892,44 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # the same steps synchronous (each call returns when its image is done; no
-    # planner overlap with the previous call): the single-call rate next to
-    # the pipelined headline
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(sync=True)
-    drain()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed_sync = time.perf_counter() - t1
-    # phase breakdown (hipEvents on the launching stream) from separate
-    # profiled steps after the timed region: profiling synchronises each call
-    _lib.profile_enable(True)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's buffer: on rank 0 the (reduced) image / sum w and the total weight
+        dump_outputs(args.dump_outputs, *bufs[(nstep[0] - 1) % 2])
+    elapsed_sync = 0.0
     phases = []
-    for _ in range(max(3, min(args.steps, 10))):
-        step(sync=True)
-        phases.append(_lib.profile_last())
-    drain()
-    torch.cuda.synchronize()
-    _lib.profile_enable(False)
+    reduced_parity = None
+    if args.full:
+        # the same steps synchronous (each call returns when its image is done; no
+        # planner overlap with the previous call): the single-call rate next to
+        # the pipelined headline
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(sync=True)
+        drain()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed_sync = time.perf_counter() - t1
+        # phase breakdown (hipEvents on the launching stream) from separate
+        # profiled steps after the timed region: profiling synchronises each call
+        _lib.profile_enable(True)
+        for _ in range(max(3, min(args.steps, 10))):
+            step(sync=True)
+            phases.append(_lib.profile_last())
+        drain()
+        torch.cuda.synchronize()
+        _lib.profile_enable(False)
     # parity of the REDUCED image at every N (outside the timed region): the
     # last step's buffer holds, on rank 0, the RCCL-reduced image / total sum w;
     # each rank sums the fp64 DFT of its own shard at 8 fixed pixels, the sums
     # are all-reduced and rank 0 compares them with that image
-    if raw is None:
+    if args.full and raw is None:
         last = bufs[(nstep[0] - 1) % 2][0]
         reduced_parity = weak_parity(uvw_d, freq_d, vis_d, wgt_d, last if rank == 0 else None, npix, px,
                                      args.wstacking, world, rank, device)
-    else:
-        reduced_parity = None
     if world > 1:
         t = torch.tensor([elapsed, elapsed_sync], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -888,12 +937,57 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = world * nvis * args.steps / elapsed / 1e6
+    P = params.nplanes
+    taps = params.support ** (3 if args.wstacking else 2)
+    result = {
+        "metric": f"Mvis/s gridded (invert) on {params.nu // 1024}k^2 grid, support={params.support}",
+        "value": round(value, 2),
+        "unit": "Mvis/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32-class (packed 2x32-bit)" if args.single else "f64",
+        "data": ("synthetic (seeded MeerKAT-like uvw tracks, raw (rows, nchan, 4) complex64 correlations, float32 "
+                 "weights, uint8 flags 2.5% per XX/YY entry)" if args.raw else
+                 "synthetic (seeded MeerKAT-like uvw tracks, random complex64 vis, float32 weights, 5% flagged)"),
+        "config": {
+            "input": ("raw linear-feed columns, Stokes I formed in the gridder (cip_ms2dirty_stokes_i)" if args.raw
+                      else "Stokes-I visibilities + effective weights (cip_ms2dirty)"),
+            "workload": (f"{args.config.upper()}: {cfg['rows']:,} rows x {cfg['nchan']} ch = {nvis:,} vis/GPU -> "
+                         f"{params.nu}x{params.nv} grid ({npix}^2 image), support {params.support}, "
+                         f"{'w-stacking ' + str(P) + ' planes' if args.wstacking else '2-D'}, "
+                         f"{'packed single-precision' if args.single else 'fp64'} accumulate"),
+            "rows_per_gpu": cfg["rows"],
+            "channels": cfg["nchan"],
+            "grid": params.nu,
+            "image": npix,
+            "support": params.support,
+            "wstacking": bool(args.wstacking),
+            "parallelism": f"uvw-shard dp{world} + RCCL image reduce" if world > 1 else "single GPU",
+            "mode": ("sync" if args.sync else
+                     "pipelined: back-to-back CIP_ASYNC|CIP_PIPELINE calls on HBM-resident, unchanged inputs "
+                     "(call k+1's planner overlaps call k's scatter/FFT); value_sync = one call at a time"),
+        },
+        "gtap_per_s": round(world * nvis * taps * args.steps / elapsed / 1e9, 2),
+        "communicator": comm,
+    }
+    if not args.full:
+        # a plain run: the headline alone
+        result.update({"roofline": None, "cpu_baseline": None})
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     avg = {k: float(np.mean([p[k] for p in phases])) for k in phases[0]}
     runs = avg["runs"]
     launches = max(avg["scatter_launches"], 1.0)
     scatter_ms = avg["scatter_ms"] / launches
-    P = params.nplanes
-    taps = params.support ** (3 if args.wstacking else 2)
     # algorithmic bytes of one scatter launch, design-independent (SURVEY.md
     # 8(d) B_alg): every visibility's value (c64, 8 B) and weight (f32, 4 B)
     # once per plane it feeds, 32 B per row slice (uvw + channel range) and the
@@ -946,47 +1040,13 @@ def main():
     if tr and not args.wstacking and not args.single and not args.raw and args.support == tr.get("support", 8):
         roofline["traffic"] = tr.get("hbm_bytes_per_launch")
 
-    result = {
-        "metric": f"Mvis/s gridded (invert) on {params.nu // 1024}k^2 grid, support={params.support}",
-        "value": round(value, 2),
-        "unit": "Mvis/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32-class (packed 2x32-bit)" if args.single else "f64",
-        "data": ("synthetic (seeded MeerKAT-like uvw tracks, raw (rows, nchan, 4) complex64 correlations, float32 "
-                 "weights, uint8 flags 2.5% per XX/YY entry)" if args.raw else
-                 "synthetic (seeded MeerKAT-like uvw tracks, random complex64 vis, float32 weights, 5% flagged)"),
-        "config": {
-            "input": ("raw linear-feed columns, Stokes I formed in the gridder (cip_ms2dirty_stokes_i)" if args.raw
-                      else "Stokes-I visibilities + effective weights (cip_ms2dirty)"),
-            "workload": (f"{args.config.upper()}: {cfg['rows']:,} rows x {cfg['nchan']} ch = {nvis:,} vis/GPU -> "
-                         f"{params.nu}x{params.nv} grid ({npix}^2 image), support {params.support}, "
-                         f"{'w-stacking ' + str(P) + ' planes' if args.wstacking else '2-D'}, "
-                         f"{'packed single-precision' if args.single else 'fp64'} accumulate"),
-            "rows_per_gpu": cfg["rows"],
-            "channels": cfg["nchan"],
-            "grid": params.nu,
-            "image": npix,
-            "support": params.support,
-            "wstacking": bool(args.wstacking),
-            "parallelism": f"uvw-shard dp{world} + RCCL image reduce" if world > 1 else "single GPU",
-            "mode": ("sync" if args.sync else
-                     "pipelined: back-to-back CIP_ASYNC|CIP_PIPELINE calls on HBM-resident, unchanged inputs "
-                     "(call k+1's planner overlaps call k's scatter/FFT); value_sync = one call at a time"),
-        },
+    result.update({
         "value_sync": round(world * nvis * args.steps / elapsed_sync / 1e6, 2),
         "ms_per_step_sync": round(elapsed_sync / args.steps * 1e3, 3),
         "roofline": roofline,
         "phases_ms": {k.replace("_ms", ""): round(v, 3) for k, v in avg.items() if k.endswith("_ms")},
         "mean_slice_len": round(avg["visibilities"] / max(runs, 1), 2),
-        "gtap_per_s": round(world * nvis * taps * args.steps / elapsed / 1e9, 2),
-    }
-    result["communicator"] = comm
+    })
     result["parity_reduced"] = reduced_parity
     default_run = raw is None and not args.wstacking and not args.single and args.config == "c3"
     secondary = {}

@@ -14,7 +14,7 @@ for rep in $(seq ${REPS:-2}); do
         env:*) export "${v#env:}" ;;
         *) export CIP_HIP_LIB=$v ;;
       esac
-      timeout -k 10 240 python bench.py --no-cpu-baseline --no-strong-secondary --no-max-err --steps ${STEPS:-10} \
+      timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-strong-secondary --no-max-err --steps ${STEPS:-10} \
           --warmup ${WARMUP:-5} ${BENCH_ARGS} > gpurun_out/ab_one.json 2> gpurun_out/ab_err.log || exit 1
       python -c "
 import json; d=json.load(open('gpurun_out/ab_one.json')); r=d.get('secondary', {}).get('reference_call')

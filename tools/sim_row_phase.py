@@ -1,5 +1,7 @@
 import sys, numpy as np
-sys.path.insert(0, "/root/repo/ska-sdp-continuum-imaging-pipeline_amd"); sys.path.insert(0, "/root/repo/tools")
+from pathlib import Path
+_TOOLS = Path(__file__).resolve().parent
+sys.path.insert(0, str(_TOOLS.parent / "ska-sdp-continuum-imaging-pipeline_amd")); sys.path.insert(0, str(_TOOLS))
 from ska_sdp_cip_amd import synthetic as syn
 from sim_bank_conflicts import origins
 rows = int(sys.argv[1]); maxw = int(sys.argv[2])
