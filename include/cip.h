@@ -12,6 +12,9 @@
  *   cip_ms2dirty       <- ducc0.wgridder.ms2dirty as called at
  *                         /root/reference/src/ska_sdp_cip/invert.py:170-183
  *                         (plus the sum of weights of invert.py:184)
+ *   cip_dirty2ms       <- ducc0.wgridder.dirty2ms, the predict half of a
+ *                         major cycle (the exact transpose of cip_ms2dirty;
+ *                         the reference leaves it to ducc0 on the CPU)
  *   cip_choose_params  <- ducc0's internal parameter choice (grid size,
  *                         kernel support, w-planes), SURVEY.md 8(a) a4.1/a4.2
  *   cip_tile_runs      <- create_uvw_tile_mapping_sequential's per-row key and
@@ -99,6 +102,11 @@ extern "C" {
                           * it every input accumulates in 64-bit fixed point
                           * (2^-46 of max|w V|, fp64 class). */
 
+#define CIP_SUBTRACT 256 /* cip_dirty2ms only: vis_io holds data on entry and
+                          * receives vis_io - wgt * model (the major cycle's
+                          * residual, formed in the degridder's epilogue);
+                          * without it vis_io is overwritten. */
+
 typedef struct cip_gridder_params {
   int64_t nu, nv;      /* oversampled grid size (cells), even, 2/3/5/7-smooth */
   int32_t support;     /* kernel support W: even 4..16, or 24/32/48/64 (2-D;
@@ -137,6 +145,34 @@ int cip_ms2dirty(const double* uvw, int64_t nrow, const double* freq,
                  int64_t npix_y, double pixsize_x, double pixsize_y,
                  double epsilon, int support, int flags,
                  void* hip_stream, double* dirty_out, double* sum_wgt_out,
+                 cip_gridder_params* params_out);
+
+/* Predict / degridding (drop-in for ducc0.wgridder.dirty2ms), the exact
+ * transpose of the operator cip_ms2dirty computes:
+ *   vis[r,c] = wgt[r,c] sum_{i,j} dirty[i,j] / n
+ *              exp(-2 pi i f_c/c (u_r l + v_r m - w_r (n - 1)))
+ * with l, m, n as for cip_ms2dirty; without CIP_WSTACKING n := 1 and the w
+ * term is dropped. All data pointers are DEVICE pointers: uvw, freq, wgt as
+ * cip_ms2dirty; dirty (npix_x, npix_y) f64, not modified; vis_io (nrow, nchan)
+ * complex64 or complex128 (the arithmetic is fp64 either way). The grid,
+ * kernel and w planes are chosen exactly as by cip_ms2dirty (returned in
+ * params_out, may be NULL). Kernel supports 4..16 only.
+ * flags: CIP_WSTACKING; CIP_SUBTRACT (vis_io -= wgt * model instead of
+ * vis_io = wgt * model); CIP_REUSE_PLAN with cip_ms2dirty's promise and
+ * matching rule - a predict after an fp64-class invert of the same uvw, freq
+ * and geometry on this thread runs through that invert's tile plan (and an
+ * invert after a predict through the predict's), else it plans as usual; the
+ * output is identical either way. CIP_ACC_SINGLE, CIP_PSF, CIP_NORMALISE,
+ * CIP_ASYNC and CIP_PIPELINE are CIP_EINVAL. A zero weight gives an exact 0
+ * (leaves vis_io untouched under CIP_SUBTRACT); nrow == 0 is a no-op. No
+ * floating-point atomics: identical calls give identical bits. Synchronous
+ * on hip_stream. cip_profile_last reports it in the invert's slots: scatter =
+ * degrid, fft = the forward FFTs, correct = image preparation. */
+int cip_dirty2ms(const double* uvw, int64_t nrow, const double* freq,
+                 int64_t nchan, const double* dirty, int64_t npix_x,
+                 int64_t npix_y, double pixsize_x, double pixsize_y,
+                 double epsilon, int support, int flags, const void* wgt,
+                 int wgt_dtype, void* hip_stream, void* vis_io, int vis_dtype,
                  cip_gridder_params* params_out);
 
 /* cip_ms2dirty restricted to w planes [plane_begin, plane_end) of the

@@ -162,6 +162,49 @@ hipError_t launch_wfinal_correct(double* acc, int64_t npix_x, int64_t npix_y, do
                                  double fw_dnu, double dw, hipStream_t s, int64_t i0 = 0, int64_t nrows = -1,
                                  const double* norm = nullptr, const float* acc_f32 = nullptr);
 
+// ---- degridding (cip_degrid.h, cip_degrid.hip) -----------------------------
+// Where a degrid launch puts its values.
+//   acc == NULL (2-D): vis_io[idx] = wt * model, or -= wt * model (subtract),
+//     in vis_io's dtype; a zero weight stores an exact 0 (leaves vis_io
+//     untouched under subtract).
+//   acc != NULL (w-stacking): acc[idx] (complex128) = / += this plane group's
+//     share of the model; launch_degrid_finish applies weight, subtraction
+//     and dtype after the last group.
+struct DegridOut {
+  void* vis_io;
+  int vis_dtype;  // CIP_C64 / CIP_C128
+  const void* wgt;
+  int wgt_dtype;  // CIP_NONE / CIP_F32 / CIP_F64
+  int subtract;
+  double2* acc;
+};
+// one kernel support W (instantiated in cip_degrid_w.hip for W = 4, 6, ..., 16)
+template <int W>
+hipError_t launch_degrid_w(int group, dim3 gd, hipStream_t s, const double* uvw, const double* fx, const RowMap& m,
+                           const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t cb,
+                           const GridGeometry& g, int64_t plane, const double* planes, const DegridOut& o);
+// work units [chunk_begin, chunk_begin + nchunks) of the plan against the
+// forward-transformed planes plane .. plane + group - 1 (nu x nv complex128
+// each, g[x][y]); reads neither perm nor the row phases
+hipError_t launch_degrid(int support, int group, const double* uvw, const double* fx, const RowMap& m,
+                         const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t chunk_begin,
+                         int64_t nchunks, const GridGeometry& g, int64_t plane, const double* planes,
+                         const DegridOut& o, hipStream_t s);
+// w-stacking: vis_io = / -= wgt * acc over nvis visibilities (acc may alias a
+// complex128 vis_io when not subtracting)
+hipError_t launch_degrid_finish(const DegridOut& o, int64_t nvis, hipStream_t s);
+// out[i, j] = (-1)^(p+q) dirty[i, j] cx[i] cy[j], in w-stacking also
+// / (F(dw |n - 1|) n) (fw_table as launch_wfinal_correct; NULL: 2-D)
+hipError_t launch_degrid_image(const double* dirty, int64_t npix_x, int64_t npix_y, double pixsize_x,
+                               double pixsize_y, const double* cx, const double* cy, const double* fw_table,
+                               int64_t fw_n, double fw_dnu, double dw, double* out, hipStream_t s);
+// np zero-padded planes (nu x nv complex128, g[x][y]) of the prepared image:
+// cell (p mod nu, q mod nv) = image[p + npix_x / 2, q + npix_y / 2], in
+// w-stacking times the conjugate screen exp(+2 pi i (w_first + k dw) (n - 1))
+// for plane k; every other cell zero
+hipError_t launch_degrid_pad(const double* image, int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y,
+                             const GridGeometry& g, double w_first, int np, double* planes, hipStream_t s);
+
 // ---- pruned 2-D FFT (cip_fft.hip) -----------------------------------------
 // gT: the grid transposed (nv rows of nu cells); H: (nx / 8) x nv x 8 complex;
 // tw_u / tw_v: exp(+2 pi i m / n), m < n (interleaved re, im).

@@ -4,12 +4,13 @@ ska_sdp_cip_amd - MI355X-native invert hot path of ska_sdp_cip.
 Public API mirrors `/root/reference/src/ska_sdp_cip/__init__.py:1-10`
 (`MeasurementSetReader`, `invert_measurement_set`,
 `dask_invert_measurement_set`, `__version__`) plus the drop-in gridder
-`ms2dirty` (replaces `ducc0.wgridder.ms2dirty`) and the `uvw_tiling` package.
+`ms2dirty` (replaces `ducc0.wgridder.ms2dirty`), its adjoint `dirty2ms`
+(`ducc0.wgridder.dirty2ms`; `predict.py` wraps it) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
 
-from .gridder import ms2dirty  # noqa: E402
+from .gridder import dirty2ms, ms2dirty  # noqa: E402
 from .invert import (  # noqa: E402
     StokesIGridderInput,
     dask_invert_measurement_set,
@@ -17,6 +18,7 @@ from .invert import (  # noqa: E402
     integrate_weighted_images,
     invert_measurement_set,
 )
+from .predict import device_residual, ducc_predict  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -47,4 +49,7 @@ __all__ = [
     "integrate_weighted_images",
     "invert_measurement_set",
     "ms2dirty",
+    "dirty2ms",
+    "ducc_predict",
+    "device_residual",
 ]

@@ -12,6 +12,10 @@ Definition computed (ducc0's documented ms2dirty):
                   exp(2 pi i f_c/c (u_r l + v_r m - w_r (n - 1))) }
 with l = (i - npix_x/2) pixsize_x, m = (j - npix_y/2) pixsize_y,
 n = sqrt(1 - l^2 - m^2); in 2-D mode (do_wstacking=False) n := 1.
+
+`dirty2ms` is its exact transpose (ducc0.wgridder.dirty2ms, `cip_dirty2ms`):
+    vis[r,c] = wgt[r,c] sum_{i,j} dirty[i,j]/n
+               exp(-2 pi i f_c/c (u_r l + v_r m - w_r (n - 1)))
 """
 
 from __future__ import annotations
@@ -421,6 +425,138 @@ def ms2dirty(  # pylint: disable=too-many-arguments,unused-argument
             single_precision_accumulation=single and double_precision_accumulation is False)
         dirty = dirty.to(torch.float32) if single else dirty
         result = dirty.cpu().numpy() if numpy_in else dirty
+    if return_params:
+        return result, params
+    return result
+
+
+def device_dirty2ms(
+    uvw: "torch.Tensor",
+    freq: "torch.Tensor",
+    dirty: "torch.Tensor",
+    wgt: Optional["torch.Tensor"],
+    pixsize_x: float,
+    pixsize_y: float,
+    *,
+    epsilon: float = 1e-4,
+    support: Optional[int] = None,
+    do_wstacking: bool = False,
+    out: Optional["torch.Tensor"] = None,
+    out_dtype=None,
+    subtract: bool = False,
+    reuse_plan: bool = False,
+) -> tuple["torch.Tensor", _lib.GridderParams]:
+    """
+    Device-resident dirty2ms (cip_dirty2ms): model visibilities of the fp64
+    image `dirty` (npix_x, npix_y) at (uvw, freq), all tensors already in HBM.
+    Returns (vis (nrow, nchan), params). `out` (complex64 / complex128)
+    receives the result, else a new tensor of `out_dtype` (default
+    complex128); the arithmetic is fp64 either way. `subtract=True`
+    (CIP_SUBTRACT, needs `out`): `out` holds data and receives
+    out - wgt * model, the major cycle's residual. `reuse_plan=True`
+    (CIP_REUSE_PLAN): as device_ms2dirty - a predict after an invert of the
+    same uvw / freq / geometry on this thread runs through that invert's tile
+    plan. Supports 4..16 only; `dirty` is not modified.
+    """
+    vis_codes, wgt_codes = _codes()
+    if out_dtype is None:
+        out_dtype = torch.complex128
+    nrow = uvw.shape[0]
+    nchan = freq.shape[0]
+    if tuple(uvw.shape) != (nrow, 3):
+        raise ValueError("uvw must have shape (nrow, 3)")
+    if uvw.dtype != torch.float64 or freq.dtype != torch.float64:
+        raise ValueError("uvw and freq must be float64")
+    if dirty.dim() != 2 or dirty.dtype != torch.float64:
+        raise ValueError(f"dirty must be a float64 (npix_x, npix_y) image, got {dirty.dtype} "
+                         f"{tuple(dirty.shape)}")
+    if wgt is not None and wgt.dtype not in wgt_codes:
+        raise ValueError(f"wgt dtype must be float32/float64, got {wgt.dtype}")
+    if wgt is not None and tuple(wgt.shape) != (nrow, nchan):
+        raise ValueError(f"wgt must have shape ({nrow}, {nchan})")
+    for t in (uvw, freq, dirty) + ((wgt,) if wgt is not None else ()):
+        _check_device_tensor(t, uvw.device, "device_dirty2ms inputs")
+    if out is None:
+        if subtract:
+            raise ValueError("subtract=True needs `out` holding the visibilities to subtract from")
+        if out_dtype not in vis_codes:
+            raise ValueError(f"out_dtype must be complex64/complex128, got {out_dtype}")
+        out = torch.empty((nrow, nchan), dtype=out_dtype, device=uvw.device)
+    else:
+        # the library writes nrow * nchan cells through the raw pointer
+        if out.dtype not in vis_codes or tuple(out.shape) != (nrow, nchan):
+            raise ValueError(f"out must be complex64/complex128 of shape ({nrow}, {nchan}), "
+                             f"got {out.dtype} {tuple(out.shape)}")
+        _check_device_tensor(out, uvw.device, "out")
+    params = _lib.GridderParams()
+    with torch.cuda.device(uvw.device):
+        stream = torch.cuda.current_stream(uvw.device).cuda_stream
+        rc = _lib.lib().cip_dirty2ms(
+            uvw.data_ptr(), nrow, freq.data_ptr(), nchan, dirty.data_ptr(), int(dirty.shape[0]),
+            int(dirty.shape[1]), float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
+            (_lib.CIP_WSTACKING if do_wstacking else 0)
+            | (_lib.CIP_SUBTRACT if subtract else 0)
+            | (_lib.CIP_REUSE_PLAN if reuse_plan else 0),
+            wgt.data_ptr() if wgt is not None else None,
+            wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
+            stream, out.data_ptr(), vis_codes[out.dtype], params)
+    _lib.check(rc)
+    return out, params
+
+
+def dirty2ms(  # pylint: disable=too-many-arguments,unused-argument
+    uvw,
+    freq,
+    dirty,
+    wgt=None,
+    pixsize_x: float = None,
+    pixsize_y: float = None,
+    nu: int = 0,
+    nv: int = 0,
+    epsilon: float = 1e-4,
+    do_wstacking: bool = False,
+    nthreads: int = 1,
+    verbosity: int = 0,
+    mask=None,
+    *,
+    support: Optional[int] = None,
+    device=None,
+    return_params: bool = False,
+):
+    """
+    Drop-in for `ducc0.wgridder.dirty2ms` (same positional order). `nu`, `nv`,
+    `nthreads` and `verbosity` are accepted for signature compatibility and
+    ignored, as in `ms2dirty`. `mask` (uint8, shape of the visibilities)
+    zeroes the weights where 0. numpy in -> numpy out, torch in -> torch out.
+    Output dtype follows ducc: complex64 for a float32 `dirty`, else
+    complex128; the arithmetic is fp64 either way.
+    """
+    _require_gpu()
+    if pixsize_x is None or pixsize_y is None:
+        raise TypeError("pixsize_x and pixsize_y are required")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    numpy_in = isinstance(dirty, np.ndarray)
+    single = dirty.dtype in (np.float32, torch.float32)
+    with torch.cuda.device(dev):
+        uvw_d = _to_device(uvw, torch.float64, dev)
+        freq_d = _to_device(np.asarray(freq, dtype=np.float64) if not torch.is_tensor(freq) else freq,
+                            torch.float64, dev)
+        dirty_d = _to_device(dirty, torch.float64, dev)
+        wgt_d = None
+        if wgt is not None:
+            wdt = torch.float32 if (wgt.dtype in (np.float32, torch.float32)) else torch.float64
+            wgt_d = _to_device(wgt, wdt, dev)
+        if mask is not None:
+            m = _to_device(np.asarray(mask) if not torch.is_tensor(mask) else mask, torch.bool, dev)
+            if wgt_d is None:
+                wgt_d = m.to(torch.float32)
+            else:
+                wgt_d = wgt_d * m.to(wgt_d.dtype)
+        vis, params = device_dirty2ms(
+            uvw_d, freq_d, dirty_d, wgt_d, float(pixsize_x), float(pixsize_y), epsilon=epsilon,
+            support=support, do_wstacking=do_wstacking,
+            out_dtype=torch.complex64 if single else torch.complex128)
+        result = vis.cpu().numpy() if numpy_in else vis
     if return_params:
         return result, params
     return result

@@ -10,6 +10,11 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
   --mode continuum  continuum_invert: Stokes I, Q, U, V dirty images + PSF on
                     a mosaic of facets (row 4, config C5's products) from
                     device-resident raw columns
+  --mode degrid     device_dirty2ms (predict, the invert's transpose) on
+                    resident synthetic data: 2-D support 8 fp64, or --refcall
+                    (epsilon 1e-4, w-stacking); also the same call through an
+                    invert's tile plan (reuse_plan) and the invert's own time
+                    on the same inputs
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -26,9 +31,63 @@ sys.path.insert(0, str(ROOT / "ska-sdp-continuum-imaging-pipeline_amd"))
 import numpy as np  # noqa: E402
 
 
+def degrid(args):
+    """ms per device_dirty2ms call on resident inputs, its profile phases, the
+    call through an invert's plan, and that invert's time."""
+    import torch
+
+    from ska_sdp_cip_amd import _lib, gridder, synthetic as syn
+
+    dev = torch.device("cuda", 0)
+    uvw_h = syn.uvw_tracks(args.rows, 64, array_radius_m=4000.0)
+    freq_h = syn.channel_frequencies(args.nchan)
+    px = syn.pixel_size_for_grid(uvw_h, freq_h, args.npix, support=8)
+    uvw, freq = torch.from_numpy(uvw_h).to(dev), torch.from_numpy(freq_h).to(dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20241008)
+    shape = (args.rows, args.nchan)
+    vis = torch.randn(shape, dtype=torch.complex64, device=dev, generator=g)
+    wgt = torch.rand(shape, dtype=torch.float32, device=dev, generator=g) + 0.5
+    image = torch.randn((args.npix, args.npix), dtype=torch.float64, device=dev, generator=g)
+    out = torch.empty(shape, dtype=torch.complex64, device=dev)
+    call = dict(epsilon=1e-4, do_wstacking=True) if args.refcall else dict(support=8, do_wstacking=False)
+    nvis = args.rows * args.nchan
+
+    def timed(fn):
+        fn()  # warm-up: workspace, FFT plan, correction tables
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.repeat):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.repeat
+
+    predict = lambda **kw: gridder.device_dirty2ms(uvw, freq, image, wgt, px, px, out=out, **call, **kw)  # noqa: E731
+    invert = lambda: gridder.device_ms2dirty(uvw, freq, vis, wgt, args.npix, args.npix, px, px, **call)  # noqa: E731
+    dt = timed(predict)
+    _lib.profile_enable(True)
+    _, params = predict()
+    prof = _lib.profile_last()
+    _lib.profile_enable(False)
+    dt_invert = timed(invert)
+    invert()  # the plan the reusing predict runs through
+    dt_reuse = timed(lambda: predict(reuse_plan=True))
+    mode = "epsilon 1e-4, w-stacking" if args.refcall else "2-D, support 8"
+    return {"data": "synthetic (real uvw tracks, random fp64 image, float32 weights, complex64 output)",
+            "rows": args.rows, "channels": args.nchan, "npix": args.npix, "visibilities": nvis,
+            "metric": f"Gvis/s predicted (device_dirty2ms, {mode}, fp64)", "value": round(nvis / dt / 1e9, 3),
+            "unit": "Gvis/s", "ms_per_call": round(dt * 1e3, 3), "support": params.support,
+            "nplanes": params.nplanes, "grid": [params.nu, params.nv],
+            "phases_ms": {k: round(v, 3) for k, v in prof.items() if k.endswith("_ms")},
+            "degrid_launches": prof["scatter_launches"], "chunks": prof["chunks"],
+            "reuse_plan_ms_per_call": round(dt_reuse * 1e3, 3),
+            "reuse_plan_gvis_per_s": round(nvis / dt_reuse / 1e9, 3),
+            "invert_ms_per_call": round(dt_invert * 1e3, 3), "invert_gvis_per_s": round(nvis / dt_invert / 1e9, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum"), required=True)
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid"), required=True)
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--npix", type=int, default=2048)
@@ -38,8 +97,8 @@ def main():
     ap.add_argument("--world", type=int, default=1,
                     help="continuum: time rank 0's share of the facets of a `world`-GPU run (k %% world == 0)")
     ap.add_argument("--refcall", action="store_true",
-                    help="continuum: the reference's gridder call (epsilon 1e-4, w-stacking, float class) "
-                         "instead of 2-D support 8 fp64")
+                    help="continuum / degrid: the reference's gridder call (epsilon 1e-4, w-stacking; continuum: "
+                         "float class) instead of 2-D support 8 fp64")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
@@ -48,6 +107,9 @@ def main():
 
     from ska_sdp_cip_amd import synthetic as syn
 
+    if args.mode == "degrid":
+        print(json.dumps(degrid(args)), flush=True)
+        return
     ms = syn.make_measurement_set(args.rows, args.nchan, n_ant=64, array_radius_m=4000.0, cheap_visibilities=True)
     uvw, freq = ms.uvw(), ms.channel_frequencies()
     px = syn.pixel_size_for_grid(uvw, freq, args.npix, support=8)
