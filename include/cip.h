@@ -15,6 +15,8 @@
  *   cip_dirty2ms       <- ducc0.wgridder.dirty2ms, the predict half of a
  *                         major cycle (the exact transpose of cip_ms2dirty;
  *                         the reference leaves it to ducc0 on the CPU)
+ *   cip_hogbom_clean   - the minor cycle between the two (Hogbom CLEAN on
+ *                         the device; the reference has no deconvolution)
  *   cip_choose_params  <- ducc0's internal parameter choice (grid size,
  *                         kernel support, w-planes), SURVEY.md 8(a) a4.1/a4.2
  *   cip_tile_runs      <- create_uvw_tile_mapping_sequential's per-row key and
@@ -174,6 +176,57 @@ int cip_dirty2ms(const double* uvw, int64_t nrow, const double* freq,
                  double epsilon, int support, int flags, const void* wgt,
                  int wgt_dtype, void* hip_stream, void* vis_io, int vis_dtype,
                  cip_gridder_params* params_out);
+
+/* Hogbom CLEAN (the minor cycle) on a real fp64 image; no reference
+ * counterpart (the reference stops at the dirty image). residual_io (nx, ny)
+ * row-major, axis 0 <-> l as everywhere here; psf (psf_nx, psf_ny) with its
+ * centre pixel at (psf_cx, psf_cy), -1: psf_n / 2, where cip_ms2dirty with
+ * CIP_PSF puts the peak. The PSF may be smaller than the image (a patch), of
+ * equal size or larger. mask (nx, ny) uint8, nonzero: the pixel may hold a
+ * component; NULL: every pixel. All data pointers are DEVICE pointers.
+ * For k = 0, 1, ...:
+ *   1. (i*, j*) = the allowed pixel with the largest |res|; ties go to the
+ *      lowest flat index i ny + j; a NaN pixel is never selected (the
+ *      comparison is >); peak = res[i*, j*] with its sign.
+ *   2. stop, before subtracting, in this order: no pixel allowed ->
+ *      CIP_CLEAN_EMPTY; |peak| <= threshold -> CIP_CLEAN_THRESHOLD (includes
+ *      a zero peak); k == niter -> CIP_CLEAN_NITER.
+ *   3. f = gain peak; model[i*, j*] += f; comp_index[k] = i* ny + j*,
+ *      comp_flux[k] = f; for every image pixel (i, j) whose PSF index
+ *      (i - i* + cx, j - j* + cy) lies inside the PSF:
+ *      res[i, j] = res[i, j] - (f psf[...]).
+ * Rounding is part of the definition: f, the product f psf and the subtraction
+ * are each one rounded fp64 operation (no FMA) and the model update one
+ * rounded add, so residual, model and component list are bit-identical to
+ * the numpy statement res[win] -= f * psf[win'].
+ * Pixels outside the mask are still subtracted. model_io (nx, ny) is
+ * accumulated into (may be NULL); comp_index / comp_flux hold niter entries
+ * each (both or neither). niter == 0 changes nothing and reports the peak.
+ * The host queues `batch` iterations (0: library default) between two
+ * readbacks of a small device state; the result does not depend on batch.
+ * Synchronous on hip_stream. No floating-point atomics.
+ * CIP_EINVAL: NULL residual_io / psf, a dimension < 1, a centre outside the
+ * PSF, gain not finite or <= 0, threshold NaN or negative, niter < 0,
+ * batch < 0, exactly one of comp_index / comp_flux. */
+#define CIP_CLEAN_NITER 0
+#define CIP_CLEAN_THRESHOLD 1
+#define CIP_CLEAN_EMPTY 2
+#define CIP_CLEAN_DEFAULT_BATCH 64 /* iterations per readback for batch == 0 */
+typedef struct cip_clean_result { /* HOST memory */
+  int64_t niter_done;  /* components written by this call */
+  int32_t stop_reason; /* CIP_CLEAN_* */
+  int32_t reserved;
+  double peak;         /* signed value of the largest |res| under the mask on
+                          exit (0 if EMPTY) */
+  int64_t peak_index;  /* its flat index, -1 if EMPTY */
+} cip_clean_result;
+int cip_hogbom_clean(double* residual_io, int64_t nx, int64_t ny,
+                     const double* psf, int64_t psf_nx, int64_t psf_ny,
+                     int64_t psf_cx, int64_t psf_cy, const uint8_t* mask,
+                     double gain, double threshold, int64_t niter,
+                     int64_t batch, void* hip_stream, double* model_io,
+                     int64_t* comp_index, double* comp_flux,
+                     cip_clean_result* result_out);
 
 /* cip_ms2dirty restricted to w planes [plane_begin, plane_end) of the
  * w-stacking stack (CIP_WSTACKING required): the multi-GPU split of ONE

@@ -1,0 +1,281 @@
+// cip_clean.hip - Hogbom CLEAN minor cycle on the device (cip_hogbom_clean,
+// DESIGN.md 12).
+//
+// The image is cut into fixed tiles of kCleanTileX rows x kCleanTileY columns
+// (4096 pixels, every row segment contiguous). A table in the workspace holds
+// each tile's (largest |res| under the mask, its flat index). One iteration is
+// two plain launches on the caller's stream:
+//   subtract: the workgroups whose tile meets the PSF window around the peak
+//             (read from the device state) subtract f * psf from the window's
+//             pixels and recompute their tile's table entry over ALL of the
+//             tile's pixels; tiles outside the window keep their entries.
+//   select:   one workgroup reduces the table (wave shuffles, then LDS),
+//             applies the stop rule, writes the component, updates the model
+//             and stores the next (i*, j*, f) in the state.
+// The host never waits per iteration: once the state says stopped every queued
+// kernel returns without touching memory, so the result does not depend on how
+// many iterations the host queues between two readbacks.
+//
+// Rounding is part of the definition (cip.h): f = gain * peak, f * psf and
+// res - (f * psf) are each one rounded fp64 operation, never an FMA, so the run
+// is bit-identical to the numpy statement res[win] -= f * psf[win'].
+#include <algorithm>
+
+#include "cip_internal.h"
+
+namespace cip {
+
+namespace {
+
+constexpr int kTX = kCleanTileX;  // tile rows
+constexpr int kTY = kCleanTileY;  // tile columns
+constexpr int kThreads = 1024;    // 16 waves: a wave covers one 128-column row as 64 column pairs
+constexpr int kWaves = kThreads / 64;
+constexpr int kSelectThreads = 1024;
+constexpr int kSelectUnroll = 8;  // table entries one select thread loads before it compares
+static_assert(kTY == 128 && kTX % kWaves == 0, "a wave covers one tile row as 64 column pairs");
+
+struct Cand {
+  double a;     // |value|; -1: nothing selected yet
+  int64_t idx;  // flat index; INT64_MAX: none
+};
+
+__device__ __forceinline__ Cand cand_none() { return {-1.0, INT64_MAX}; }
+
+// `>` keeps NaN out (every comparison with it is false); ties go to the lower
+// flat index, so any reduction order gives the same winner
+__device__ __forceinline__ void cand_take(Cand& b, double a, int64_t idx) {
+  if (a > b.a || (a == b.a && idx < b.idx)) {
+    b.a = a;
+    b.idx = idx;
+  }
+}
+
+__device__ __forceinline__ Cand wave_best(Cand c) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double a = __shfl_down(c.a, off, 64);
+    const long long i = __shfl_down((long long)c.idx, off, 64);
+    cand_take(c, a, (int64_t)i);
+  }
+  return c;  // lane 0 holds the wave's best
+}
+
+// the workgroup's best in thread 0 (nwaves <= 16)
+template <int NWAVES>
+__device__ __forceinline__ Cand block_best(Cand c) {
+  __shared__ double s_a[NWAVES];
+  __shared__ long long s_i[NWAVES];
+  c = wave_best(c);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    s_a[wave] = c.a;
+    s_i[wave] = (long long)c.idx;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    Cand d = cand_none();
+    if (lane < NWAVES) {
+      d.a = s_a[lane];
+      d.idx = (int64_t)s_i[lane];
+    }
+    c = wave_best(d);
+  }
+  return c;
+}
+
+// one rounded multiply, one rounded subtract: contraction is off for this
+// expression (hipcc contracts a * b - c into an FMA by default)
+__device__ __forceinline__ double sub_rounded(double r, double f, double p) {
+#pragma clang fp contract(off)
+  const double prod = f * p;
+  return r - prod;
+}
+
+__device__ __forceinline__ double add_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// One tile (tx, ty) by one workgroup: with SUB, res -= f * psf on the pixels
+// inside the PSF window around (pi, pj); then the tile's table entry over all
+// of its pixels.
+template <bool SUB>
+__device__ __forceinline__ void tile_pass(double* __restrict__ res, int64_t nx, int64_t ny, int64_t tx, int64_t ty,
+                                          int64_t nty, const double* __restrict__ psf, int64_t px, int64_t py,
+                                          int64_t oi, int64_t oj, double f, const uint8_t* __restrict__ mask,
+                                          CleanEntry* __restrict__ table) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t j = ty * kTY + 2 * lane;
+  // 16-byte accesses where every row of the image starts 16-byte aligned
+  const bool vec = ((ny & 1) == 0) && (((uintptr_t)res & 15u) == 0u) && (j + 1 < ny);
+  Cand best = cand_none();
+#pragma unroll
+  for (int r = 0; r < kTX / kWaves; ++r) {
+    const int64_t i = tx * kTX + wave + kWaves * r;
+    if (i >= nx || j >= ny) continue;
+    const int64_t idx = i * ny + j;
+    const bool two = j + 1 < ny;
+    double v0, v1 = 0.0;
+    if (vec) {
+      const double2 v = *reinterpret_cast<const double2*>(res + idx);
+      v0 = v.x;
+      v1 = v.y;
+    } else {
+      v0 = res[idx];
+      if (two) v1 = res[idx + 1];
+    }
+    if (SUB) {
+      // PSF index of pixel (i, j): (i - oi, j - oj), oi = i* - cx, oj = j* - cy
+      const int64_t pr = i - oi, pc = j - oj;
+      if (pr >= 0 && pr < px) {
+        const double* prow = psf + pr * py;
+        const bool in0 = pc >= 0 && pc < py;
+        const bool in1 = two && pc + 1 >= 0 && pc + 1 < py;
+        if (in0) v0 = sub_rounded(v0, f, prow[pc]);
+        if (in1) v1 = sub_rounded(v1, f, prow[pc + 1]);
+        if (vec && in0 && in1) {
+          *reinterpret_cast<double2*>(res + idx) = make_double2(v0, v1);
+        } else {
+          if (in0) res[idx] = v0;
+          if (in1) res[idx + 1] = v1;
+        }
+      }
+    }
+    if (mask) {
+      if (mask[idx]) cand_take(best, fabs(v0), idx);
+      if (two && mask[idx + 1]) cand_take(best, fabs(v1), idx + 1);
+    } else {
+      cand_take(best, fabs(v0), idx);
+      if (two) cand_take(best, fabs(v1), idx + 1);
+    }
+  }
+  best = block_best<kWaves>(best);
+  if (threadIdx.x == 0) {
+    CleanEntry e;
+    e.absmax = best.a;
+    e.index = best.idx == INT64_MAX ? (int64_t)-1 : best.idx;
+    table[tx * nty + ty] = e;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void clean_init_kernel(double* res, int64_t nx, int64_t ny, int64_t nty,
+                                                             const uint8_t* mask, CleanEntry* table) {
+  const int64_t t = blockIdx.x;
+  tile_pass<false>(res, nx, ny, t / nty, t % nty, nty, nullptr, 0, 0, 0, 0, 0.0, mask, table);
+}
+
+// grid: gx * gy workgroups, sized by the host from the PSF and image shapes
+// alone; workgroup (bx, by) takes the tile (first tile row of the window + bx,
+// first tile column + by) and leaves when that tile does not meet the window
+__global__ __launch_bounds__(kThreads) void clean_subtract_kernel(double* res, int64_t nx, int64_t ny, int64_t nty,
+                                                                 const double* psf, int64_t px, int64_t py,
+                                                                 int64_t cx, int64_t cy, int64_t gy,
+                                                                 const uint8_t* mask, CleanEntry* table,
+                                                                 const CleanState* state) {
+  if (state->stopped) return;
+  const int64_t oi = state->pi - cx, oj = state->pj - cy;
+  const double f = state->f;
+  // the window in image coordinates (never empty: 0 <= c < p and 0 <= peak < n)
+  const int64_t i_lo = oi > 0 ? oi : 0, i_hi = oi + px < nx ? oi + px : nx;
+  const int64_t j_lo = oj > 0 ? oj : 0, j_hi = oj + py < ny ? oj + py : ny;
+  const int64_t bx = (int64_t)blockIdx.x / gy, by = (int64_t)blockIdx.x % gy;
+  const int64_t tx = i_lo / kTX + bx, ty = j_lo / kTY + by;
+  if (tx * kTX >= i_hi || ty * kTY >= j_hi) return;
+  tile_pass<true>(res, nx, ny, tx, ty, nty, psf, px, py, oi, oj, f, mask, table);
+}
+
+__global__ __launch_bounds__(kSelectThreads) void clean_select_kernel(const double* res, const CleanEntry* table,
+                                                                     int64_t ntiles, double gain, double threshold,
+                                                                     int64_t niter, int64_t ny, double* model,
+                                                                     int64_t* comp_index, double* comp_flux,
+                                                                     CleanState* state) {
+  if (state->stopped) return;
+  Cand best = cand_none();
+  // one 16-byte load per entry, kSelectUnroll of them in flight per thread: a
+  // single workgroup reads the whole table, so its time is load latency over
+  // the loads it keeps outstanding
+  for (int64_t base = threadIdx.x; base < ntiles; base += (int64_t)kSelectUnroll * kSelectThreads) {
+    double2 raw[kSelectUnroll];
+#pragma unroll
+    for (int u = 0; u < kSelectUnroll; ++u) {
+      const int64_t t = base + (int64_t)u * kSelectThreads;
+      raw[u] = t < ntiles ? *reinterpret_cast<const double2*>(table + t) : make_double2(-1.0, __longlong_as_double(-1));
+    }
+#pragma unroll
+    for (int u = 0; u < kSelectUnroll; ++u) {
+      const int64_t idx = (int64_t)__double_as_longlong(raw[u].y);
+      if (idx >= 0) cand_take(best, raw[u].x, idx);
+    }
+  }
+  best = block_best<kSelectThreads / 64>(best);
+  if (threadIdx.x != 0) return;
+  const int64_t k = state->k;
+  if (best.idx == INT64_MAX) {
+    state->stopped = 1;
+    state->reason = CIP_CLEAN_EMPTY;
+    state->peak = 0.0;
+    state->peak_index = -1;
+    return;
+  }
+  const double peak = res[best.idx];
+  if (best.a <= threshold || k == niter) {
+    state->stopped = 1;
+    state->reason = best.a <= threshold ? CIP_CLEAN_THRESHOLD : CIP_CLEAN_NITER;
+    state->peak = peak;
+    state->peak_index = best.idx;
+    return;
+  }
+  const double f = mul_rounded(gain, peak);
+  if (model) model[best.idx] = add_rounded(model[best.idx], f);
+  if (comp_index) {
+    comp_index[k] = best.idx;
+    comp_flux[k] = f;
+  }
+  state->pi = best.idx / ny;
+  state->pj = best.idx % ny;
+  state->f = f;
+  state->k = k + 1;
+}
+
+}  // namespace
+
+int64_t clean_tiles(int64_t nx, int64_t ny) { return ((nx + kTX - 1) / kTX) * ((ny + kTY - 1) / kTY); }
+
+hipError_t launch_clean_init(double* res, int64_t nx, int64_t ny, const uint8_t* mask, CleanEntry* table,
+                             CleanState* state, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(state, 0, sizeof(CleanState), s);
+  if (e != hipSuccess) return e;
+  const int64_t nty = (ny + kTY - 1) / kTY;
+  clean_init_kernel<<<dim3((unsigned)clean_tiles(nx, ny)), dim3(kThreads), 0, s>>>(res, nx, ny, nty, mask, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_clean_subtract(double* res, int64_t nx, int64_t ny, const double* psf, int64_t px, int64_t py,
+                                 int64_t cx, int64_t cy, const uint8_t* mask, CleanEntry* table,
+                                 const CleanState* state, hipStream_t s) {
+  // the tiles a px x py window can meet: its extent plus one tile of slack per
+  // axis for a window that does not start on a tile edge, never more than the
+  // image has (the host does not know the peak)
+  const int64_t ntx = (nx + kTX - 1) / kTX, nty = (ny + kTY - 1) / kTY;
+  const int64_t gx = std::min<int64_t>(ntx, (std::min(px, nx) + kTX - 1) / kTX + 1);
+  const int64_t gy = std::min<int64_t>(nty, (std::min(py, ny) + kTY - 1) / kTY + 1);
+  clean_subtract_kernel<<<dim3((unsigned)(gx * gy)), dim3(kThreads), 0, s>>>(res, nx, ny, nty, psf, px, py, cx, cy, gy,
+                                                                             mask, table, state);
+  return hipGetLastError();
+}
+
+hipError_t launch_clean_select(const double* res, int64_t nx, int64_t ny, const CleanEntry* table, double gain,
+                               double threshold, int64_t niter, double* model, int64_t* comp_index, double* comp_flux,
+                               CleanState* state, hipStream_t s) {
+  clean_select_kernel<<<dim3(1), dim3(kSelectThreads), 0, s>>>(res, table, clean_tiles(nx, ny), gain, threshold, niter,
+                                                               ny, model, comp_index, comp_flux, state);
+  return hipGetLastError();
+}
+
+}  // namespace cip

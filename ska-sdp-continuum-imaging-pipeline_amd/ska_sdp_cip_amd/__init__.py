@@ -5,7 +5,9 @@ Public API mirrors `/root/reference/src/ska_sdp_cip/__init__.py:1-10`
 (`MeasurementSetReader`, `invert_measurement_set`,
 `dask_invert_measurement_set`, `__version__`) plus the drop-in gridder
 `ms2dirty` (replaces `ducc0.wgridder.ms2dirty`), its adjoint `dirty2ms`
-(`ducc0.wgridder.dirty2ms`; `predict.py` wraps it) and the `uvw_tiling` package.
+(`ducc0.wgridder.dirty2ms`; `predict.py` wraps it), the minor and major cycle
+built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`) and the
+`uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -19,6 +21,7 @@ from .invert import (  # noqa: E402
     invert_measurement_set,
 )
 from .predict import device_residual, ducc_predict  # noqa: E402
+from .deconvolve import device_hogbom_clean, device_major_cycles, hogbom_clean  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -52,4 +55,7 @@ __all__ = [
     "dirty2ms",
     "ducc_predict",
     "device_residual",
+    "hogbom_clean",
+    "device_hogbom_clean",
+    "device_major_cycles",
 ]

@@ -36,6 +36,11 @@ CIP_PIPELINE = 32
 CIP_REUSE_PLAN = 64
 CIP_GRID_ZEROED = 128
 CIP_SUBTRACT = 256
+CIP_CLEAN_NITER = 0
+CIP_CLEAN_THRESHOLD = 1
+CIP_CLEAN_EMPTY = 2
+CIP_CLEAN_DEFAULT_BATCH = 64
+CLEAN_STOP_REASONS = {CIP_CLEAN_NITER: "niter", CIP_CLEAN_THRESHOLD: "threshold", CIP_CLEAN_EMPTY: "empty"}
 STOKES_CODES = {"I": 0, "Q": 1, "U": 2, "V": 3}
 
 # every symbol declared in include/cip.h
@@ -43,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "cip_choose_params",
     "cip_ms2dirty",
     "cip_dirty2ms",
+    "cip_hogbom_clean",
     "cip_ms2dirty_stokes_i",
     "cip_grid_plane",
     "cip_grid_layout",
@@ -104,6 +110,18 @@ class GridderParams(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class CleanResult(ctypes.Structure):
+    """Mirror of `cip_clean_result` (include/cip.h)."""
+
+    _fields_ = [
+        ("niter_done", ctypes.c_int64),
+        ("stop_reason", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("peak", ctypes.c_double),
+        ("peak_index", ctypes.c_int64),
+    ]
+
+
 _LIB = None
 
 _vp = ctypes.c_void_p
@@ -131,6 +149,8 @@ def lib() -> ctypes.CDLL:
                                 _f64, _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
     so.cip_dirty2ms.argtypes = [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _f64, _f64, _f64, _i32, _i32, _vp, _i32,
                                 _vp, _vp, _i32, ctypes.POINTER(GridderParams)]
+    so.cip_hogbom_clean.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _f64, _f64, _i64, _i64, _vp,
+                                    _vp, _vp, _vp, ctypes.POINTER(CleanResult)]
     so.cip_ms2dirty_wplanes.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _f64, _f64,
                                         _f64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
     so.cip_ms2dirty_stokes_i.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _f64, _f64,
@@ -177,7 +197,7 @@ def lib() -> ctypes.CDLL:
     so.cip_profile_last.argtypes = [_vp, _vp]
     so.cip_last_error.restype = ctypes.c_char_p
     so.cip_build_info.restype = ctypes.c_char_p
-    for name in ("cip_choose_params", "cip_ms2dirty", "cip_dirty2ms", "cip_ms2dirty_stokes_i", "cip_grid_plane", "cip_grid_layout", "cip_plane_group", "cip_grid_ms", "cip_grid_ms_stokes_i",
+    for name in ("cip_choose_params", "cip_ms2dirty", "cip_dirty2ms", "cip_hogbom_clean", "cip_ms2dirty_stokes_i", "cip_grid_plane", "cip_grid_layout", "cip_plane_group", "cip_grid_ms", "cip_grid_ms_stokes_i",
                  "cip_grid_tiles", "cip_grid_tiles_strip", "cip_grid_tiles_strip_mask", "cip_strip_histogram",
                  "cip_strip_split", "cip_ms2dirty_wplanes", "cip_grid_to_dirty", "cip_strip_rows", "cip_strip_rows_masked", "cip_strip_cols", "cip_strip_cols_wplane", "cip_strip_wfinal", "cip_strip_pack_rows", "cip_strip_unpack_rows", "cip_strip_rows_packed", "cip_tile_runs",
                  "cip_stokes_i", "cip_stokes", "cip_facet_rephase", "cip_allreduce_grid", "cip_release_collectives",

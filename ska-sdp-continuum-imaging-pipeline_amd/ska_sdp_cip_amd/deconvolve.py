@@ -1,0 +1,219 @@
+"""
+Deconvolution: Hogbom CLEAN on the GPU (`cip_hogbom_clean`) and the
+device-resident major-cycle loop that joins it to the invert
+(`cip_ms2dirty`) and the predict (`cip_dirty2ms`).
+
+The operator is defined exactly in include/cip.h: peak under the mask (ties
+to the lowest flat index, NaN never selected), stop rule checked before
+subtracting, `res[win] -= f * psf[win']` with every product rounded before it
+is subtracted, so a run is bit-identical to that numpy statement.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .gridder import _check_device_tensor, _require_gpu, _to_device, device_ms2dirty
+from .invert import DO_WSTACKING, EPSILON
+from .predict import device_residual
+
+try:
+    import torch
+except ModuleNotFoundError:  # pragma: no cover - torch is in the image
+    torch = None
+
+
+def device_hogbom_clean(
+    residual: "torch.Tensor",
+    psf: "torch.Tensor",
+    *,
+    gain: float = 0.1,
+    threshold: float = 0.0,
+    niter: int = 1000,
+    mask: Optional["torch.Tensor"] = None,
+    model: Optional["torch.Tensor"] = None,
+    psf_centre: Optional[tuple] = None,
+    inplace: bool = False,
+    return_components: bool = False,
+    batch: int = 0,
+):
+    """
+    Hogbom CLEAN of the device float64 image `residual` (nx, ny) with `psf`
+    (px, py), whose centre pixel is `psf_centre` (default (px // 2, py // 2),
+    where `device_ms2dirty(psf=True)` puts the peak). Returns
+    (model, residual, info).
+
+    `mask` (nx, ny) uint8 / bool: nonzero where a component may be placed
+    (pixels outside it are still subtracted). `model` is accumulated into
+    (None: zeros). `inplace=False` works on a clone of `residual`. `info` holds
+    `niter_done`, `stop_reason` (CIP_CLEAN_*), `stop` (its name), `peak`
+    (signed value of the largest |residual| under the mask on exit) and
+    `peak_index` (flat index, -1 when no pixel is allowed); with
+    `return_components=True` also `comp_index` (int64) and `comp_flux`
+    (float64) of length `niter_done`. `batch`: iterations queued between two
+    readbacks of the device state (0: library default); the result does not
+    depend on it.
+    """
+    _require_gpu()
+    if residual.dim() != 2 or residual.dtype != torch.float64:
+        raise ValueError(f"residual must be a float64 (nx, ny) image, got {residual.dtype} {tuple(residual.shape)}")
+    if psf.dim() != 2 or psf.dtype != torch.float64:
+        raise ValueError(f"psf must be a float64 (px, py) image, got {psf.dtype} {tuple(psf.shape)}")
+    dev = residual.device
+    _check_device_tensor(residual, dev, "residual")
+    _check_device_tensor(psf, dev, "psf")
+    shape = tuple(residual.shape)
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != shape:
+            raise ValueError(f"mask must be uint8 / bool of shape {shape}")
+        _check_device_tensor(mask, dev, "mask")
+    if model is not None:
+        if model.dtype != torch.float64 or tuple(model.shape) != shape:
+            raise ValueError(f"model must be float64 of shape {shape}")
+        _check_device_tensor(model, dev, "model")
+    cx, cy = (-1, -1) if psf_centre is None else (int(psf_centre[0]), int(psf_centre[1]))
+    if psf_centre is not None and (cx < 0 or cy < 0):
+        raise ValueError("psf_centre must lie inside the PSF")
+    niter = int(niter)
+    res = residual if inplace else residual.clone()
+    if model is None:
+        model = torch.zeros(shape, dtype=torch.float64, device=dev)
+    comp_index = comp_flux = None
+    if return_components:
+        comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
+        comp_flux = torch.empty(max(niter, 1), dtype=torch.float64, device=dev)
+    result = _lib.CleanResult()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = _lib.lib().cip_hogbom_clean(
+            res.data_ptr(), shape[0], shape[1], psf.data_ptr(), int(psf.shape[0]), int(psf.shape[1]), cx, cy,
+            None if mask is None else mask.data_ptr(), float(gain), float(threshold), niter, int(batch), stream,
+            model.data_ptr(), None if comp_index is None else comp_index.data_ptr(),
+            None if comp_flux is None else comp_flux.data_ptr(), ctypes.byref(result))
+    _lib.check(rc)
+    info = {
+        "niter_done": int(result.niter_done),
+        "stop_reason": int(result.stop_reason),
+        "stop": _lib.CLEAN_STOP_REASONS[int(result.stop_reason)],
+        "peak": float(result.peak),
+        "peak_index": int(result.peak_index),
+    }
+    if return_components:
+        info["comp_index"] = comp_index[: info["niter_done"]]
+        info["comp_flux"] = comp_flux[: info["niter_done"]]
+    return model, res, info
+
+
+def hogbom_clean(
+    residual,
+    psf,
+    *,
+    gain: float = 0.1,
+    threshold: float = 0.0,
+    niter: int = 1000,
+    mask=None,
+    model=None,
+    psf_centre: Optional[tuple] = None,
+    return_components: bool = False,
+    batch: int = 0,
+    device=None,
+):
+    """
+    `device_hogbom_clean` for host or device arrays: numpy in -> numpy out,
+    torch in -> torch out (on the GPU). The inputs are never modified. Returns
+    (model, residual, info) as `device_hogbom_clean`.
+    """
+    _require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    numpy_in = isinstance(residual, np.ndarray)
+    with torch.cuda.device(dev):
+        res_d = _to_device(residual, torch.float64, dev)
+        psf_d = _to_device(psf, torch.float64, dev)
+        mask_d = None
+        if mask is not None:
+            m = np.asarray(mask) if not torch.is_tensor(mask) else mask
+            mask_d = _to_device(m != 0, torch.bool, dev)
+        model_d = None if model is None else _to_device(model, torch.float64, dev).clone()
+        model_d, res_d, info = device_hogbom_clean(
+            res_d, psf_d, gain=gain, threshold=threshold, niter=niter, mask=mask_d, model=model_d,
+            psf_centre=psf_centre, inplace=False, return_components=return_components, batch=batch)
+        if numpy_in:
+            model_d, res_d = model_d.cpu().numpy(), res_d.cpu().numpy()
+            if return_components:
+                info["comp_index"] = info["comp_index"].cpu().numpy()
+                info["comp_flux"] = info["comp_flux"].cpu().numpy()
+    return model_d, res_d, info
+
+
+def device_major_cycles(
+    uvw: "torch.Tensor",
+    freq: "torch.Tensor",
+    vis: "torch.Tensor",
+    wgt: Optional["torch.Tensor"],
+    npix: int,
+    pixsize: float,
+    *,
+    n_major: int,
+    niter: int,
+    gain: float = 0.1,
+    threshold: float = 0.0,
+    cycle_fraction: float = 0.0,
+    mask: Optional["torch.Tensor"] = None,
+    epsilon: float = EPSILON,
+    do_wstacking: bool = DO_WSTACKING,
+    support: Optional[int] = None,
+):
+    """
+    Major cycles on device-resident data (an `npix` x `npix` image with pixels
+    of `pixsize` radians); nothing leaves the GPU but a few scalars per cycle.
+
+    The PSF and the dirty image are normalised inverts (`device_ms2dirty`;
+    the second reuses the first's tile plan). Each of up to `n_major` cycles
+    CLEANs the residual image down to max(threshold, cycle_fraction * |peak at
+    the cycle's start|) with at most `niter` components, accumulating into one
+    model; then the residual visibilities `vis - dirty2ms(model)`
+    (`device_residual`, unweighted: the invert applies `wgt`) are re-inverted,
+    both through the same tile plan. The residual CLEAN leaves behind is
+    discarded in favour of the re-inverted one. The loop ends early once a
+    cycle starts at or below `threshold`.
+
+    Returns a dict: `model`, `residual` (image), `psf`, `peaks` (|peak| at the
+    start of each cycle run), `components` (count per cycle) and `stop_reason`
+    ("threshold": a cycle started at or below it; "n_major": the cycles ran
+    out; "empty": the mask allows no pixel).
+    """
+    _require_gpu()
+    npix = int(npix)
+    kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
+    psf, _ = device_ms2dirty(uvw, freq, None, wgt, npix, npix, pixsize, pixsize, psf=True, normalise=True, **kw)
+    residual, _ = device_ms2dirty(uvw, freq, vis, wgt, npix, npix, pixsize, pixsize, normalise=True,
+                                  reuse_plan=True, **kw)
+    model = torch.zeros((npix, npix), dtype=torch.float64, device=uvw.device)
+    peaks, components = [], []
+    stop_reason = "n_major"
+    for _cycle in range(int(n_major)):
+        # niter=0: the peak under the mask, nothing changed
+        _, _, start = device_hogbom_clean(residual, psf, gain=gain, threshold=threshold, niter=0, mask=mask,
+                                          inplace=True)
+        if start["stop_reason"] == _lib.CIP_CLEAN_EMPTY:
+            stop_reason = "empty"
+            break
+        peak = abs(start["peak"])
+        if peak <= threshold:
+            stop_reason = "threshold"
+            break
+        peaks.append(peak)
+        _, _, info = device_hogbom_clean(residual, psf, gain=gain, threshold=max(threshold, cycle_fraction * peak),
+                                         niter=niter, mask=mask, model=model, inplace=True)
+        components.append(info["niter_done"])
+        vis_res = device_residual(uvw, freq, vis, model, pixsize, None, reuse_plan=True, **kw)
+        device_ms2dirty(uvw, freq, vis_res, wgt, npix, npix, pixsize, pixsize, normalise=True, reuse_plan=True,
+                        out=residual, **kw)
+    return {"model": model, "residual": residual, "psf": psf, "peaks": peaks, "components": components,
+            "stop_reason": stop_reason}
