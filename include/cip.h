@@ -353,7 +353,8 @@ int cip_grid_tiles_strip(const double* slice_uvw, const int32_t* chan_start,
  * each work unit's flush) plus every tile of the tile rows holding grid rows
  * row0 .. row0 + W - 2 (the previous rank's halo is added there). Replaces
  * strips.py's torch restatement of the mask (round 5) - every call computes
- * its own. */
+ * its own. tile_bits is valid only for a strip buffer that was all zero
+ * before the call: it names this call's writes, not what the buffer held. */
 int cip_grid_tiles_strip_mask(const double* slice_uvw, const int32_t* chan_start,
                               const int32_t* chan_stop, int64_t nslices,
                               const double* freq, int64_t nchan, const void* vis,

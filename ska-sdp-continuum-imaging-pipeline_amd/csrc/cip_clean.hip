@@ -21,7 +21,7 @@
 // is bit-identical to the numpy statement res[win] -= f * psf[win'].
 #include <algorithm>
 
-#include "cip_internal.h"
+#include "cip_host.h"
 
 namespace cip {
 
@@ -279,3 +279,80 @@ hipError_t launch_clean_select(const double* res, int64_t nx, int64_t ny, const 
 }
 
 }  // namespace cip
+
+// ------------------------------------------------------------ host API ----
+namespace cip {
+
+// Hogbom CLEAN (cip_hogbom_clean): init builds the tile table,
+// then select and (subtract, select) pairs are queued `batch` iterations at a
+// time; the device state is read back once per batch. Kernels queued behind a
+// stop return at once, so the result does not depend on `batch`.
+static int hogbom_clean_impl(double* res, int64_t nx, int64_t ny, const double* psf, int64_t px, int64_t py,
+                             int64_t cx, int64_t cy, const uint8_t* mask, double gain, double threshold,
+                             int64_t niter, int64_t batch, void* hip_stream, double* model, int64_t* comp_index,
+                             double* comp_flux, cip_clean_result* result_out) {
+  if (!res || !psf) return set_error(CIP_EINVAL, "cip_hogbom_clean: residual_io and psf must not be NULL");
+  if (nx < 1 || ny < 1 || px < 1 || py < 1)
+    return set_error(CIP_EINVAL, "cip_hogbom_clean: image and PSF dimensions must be >= 1");
+  if (cx == -1) cx = px / 2;
+  if (cy == -1) cy = py / 2;
+  if (cx < 0 || cx >= px || cy < 0 || cy >= py)
+    return set_error(CIP_EINVAL, "cip_hogbom_clean: the PSF centre lies outside the PSF");
+  if (!std::isfinite(gain) || !(gain > 0.0)) return set_error(CIP_EINVAL, "cip_hogbom_clean: gain must be finite and > 0");
+  if (std::isnan(threshold) || threshold < 0.0)
+    return set_error(CIP_EINVAL, "cip_hogbom_clean: threshold must be >= 0 and not NaN");
+  if (niter < 0 || batch < 0) return set_error(CIP_EINVAL, "cip_hogbom_clean: niter and batch must be >= 0");
+  if ((comp_index == nullptr) != (comp_flux == nullptr))
+    return set_error(CIP_EINVAL, "cip_hogbom_clean: comp_index and comp_flux go together (both or neither)");
+  if (nx > INT64_MAX / ny || px > INT64_MAX / py)
+    return set_error(CIP_EINVAL, "cip_hogbom_clean: image or PSF too large");
+  const int64_t ntiles = clean_tiles(nx, ny);
+  if (ntiles >= ((int64_t)1 << 31)) return set_error(CIP_EINVAL, "cip_hogbom_clean: image has 2^31 tiles or more");
+  if (batch == 0) batch = CIP_CLEAN_DEFAULT_BATCH;
+  CIP_BEGIN_CALL(hip_stream, false)
+  CIP_ALLOC(table, CleanEntry, "clean_table", ntiles)
+  CIP_ALLOC(state, CleanState, "clean_state", 1)
+  CleanState* h = (CleanState*)pinned(ws, sizeof(CleanState));
+  if (!h) return CIP_ENOMEM;
+  CIP_HIP_CHECK(launch_clean_init(res, nx, ny, mask, table, state, s));
+  CIP_HIP_CHECK(launch_clean_select(res, nx, ny, table, gain, threshold, niter, model, comp_index, comp_flux, state, s));
+  for (int64_t queued = 0;;) {
+    const int64_t n = std::min(batch, niter - queued);
+    for (int64_t q = 0; q < n; ++q) {
+      CIP_HIP_CHECK(launch_clean_subtract(res, nx, ny, psf, px, py, cx, cy, mask, table, state, s));
+      CIP_HIP_CHECK(
+          launch_clean_select(res, nx, ny, table, gain, threshold, niter, model, comp_index, comp_flux, state, s));
+    }
+    queued += n;
+    CIP_HIP_CHECK(hipMemcpyAsync(h, state, sizeof(CleanState), hipMemcpyDeviceToHost, s));
+    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    if (h->stopped) break;
+    // after niter pairs the last select saw k == niter and stopped
+    if (queued >= niter) return set_error(CIP_EHIP, "cip_hogbom_clean: the device state did not stop");
+  }
+  if (result_out) {
+    result_out->niter_done = h->k;
+    result_out->stop_reason = h->reason;
+    result_out->reserved = 0;
+    result_out->peak = h->peak;
+    result_out->peak_index = h->peak_index;
+  }
+  return CIP_OK;
+}
+
+}  // namespace cip
+
+using namespace cip;
+
+extern "C" {
+
+int cip_hogbom_clean(double* residual_io, int64_t nx, int64_t ny, const double* psf, int64_t psf_nx, int64_t psf_ny,
+                     int64_t psf_cx, int64_t psf_cy, const uint8_t* mask, double gain, double threshold,
+                     int64_t niter, int64_t batch, void* hip_stream, double* model_io, int64_t* comp_index,
+                     double* comp_flux, cip_clean_result* result_out) {
+  clear_error();
+  return hogbom_clean_impl(residual_io, nx, ny, psf, psf_nx, psf_ny, psf_cx, psf_cy, mask, gain, threshold, niter,
+                           batch, hip_stream, model_io, comp_index, comp_flux, result_out);
+}
+
+}  // extern "C"

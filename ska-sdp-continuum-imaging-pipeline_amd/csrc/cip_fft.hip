@@ -699,16 +699,6 @@ __global__ __launch_bounds__(NH / 16, 4) void fft_cols_eo_kernel(const double2* 
   }
 }
 
-// CIP_FFT_F32=0: the packed class's complex64 planes transformed in fp64
-// (the round-4 form); default: in fp32, the class's own precision
-bool fft_f32_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("CIP_FFT_F32");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 static bool fft_len_ok(int64_t n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192 || n == 16384; }
 
 bool fast_fft_supported(int64_t nu, int64_t nv, int64_t nx, int64_t ny) {

@@ -287,15 +287,6 @@ __global__ __launch_bounds__(kOrderThreads, 8) void order_kernel(const uint8_t* 
     if (cls[k] < 32u) ((Entry*)perm)[sb + s_S[rk[k]] + __popc(s_M[rk[k]] & ((1u << cls[k]) - 1u))] = packed[k];
 }
 
-// CIP_ORDER_CLASSES=32: bank classes mod 32 (rounds 1-6) instead of mod 16 (A/B)
-static bool order_classes32() {
-  static const bool on = [] {
-    const char* e = getenv("CIP_ORDER_CLASSES");
-    return e && e[0] == '3';
-  }();
-  return on;
-}
-
 // Row phases apply when the entries have a bit to spare (bit 31 of dense
 // entries, bit 63 of ragged ones - the packed (index, row, channel) form must
 // leave it free) and the lane scatter's support gives a full cycle (dP = (T +

@@ -1,0 +1,263 @@
+// cip_host.h - what the host-side units of libcip_hip.so share (cip_workspace,
+// cip_params, cip_planner, cip_invert, cip_predict and the entry points kept
+// beside their launchers in cip_clean, cip_strips, cip_tiling): the per-thread
+// workspace, the planner's request and result, the call scope and the CIP_*
+// switches. Host only and not part of the C ABI (include/cip.h is); units
+// that hold nothing but kernels and launchers include cip_internal.h alone.
+#pragma once
+#include <hipfft/hipfft.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include "cip_internal.h"
+
+namespace cip {
+
+// ----------------------------------------------------------- profiler ----
+// hipEvents recorded on the call's stream around each phase (cip_profile_*).
+struct Profiler {
+  bool on = false;
+  int device = -1;
+  std::vector<hipEvent_t> pool;
+  size_t used = 0;
+  struct Span {
+    int phase;
+    hipEvent_t a, b;
+  };
+  std::vector<Span> spans;
+  double ms[CIP_PROFILE_PHASES] = {0};
+  int64_t counts[CIP_PROFILE_COUNTS] = {0};
+
+  void reset() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev != device) {  // events belong to a device
+      for (auto e : pool) (void)hipEventDestroy(e);
+      pool.clear();
+      device = dev;
+    }
+    used = 0;
+    spans.clear();
+    for (auto& m : ms) m = 0.0;
+    for (auto& c : counts) c = 0;
+  }
+  hipEvent_t mark(hipStream_t s) {
+    if (!on) return nullptr;
+    if (used == pool.size()) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return nullptr;
+      pool.push_back(e);
+    }
+    hipEvent_t e = pool[used++];
+    if (hipEventRecord(e, s) != hipSuccess) return nullptr;
+    return e;
+  }
+  void span(int phase, hipEvent_t a, hipEvent_t b) {
+    if (on && a && b) spans.push_back({phase, a, b});
+  }
+  void finish() {  // stream already synchronised
+    if (!on) return;
+    for (auto& sp : spans) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) ms[sp.phase] += t;
+    }
+  }
+};
+extern thread_local Profiler g_prof;  // cip_workspace.hip
+
+// ---------------------------------------------------------- workspace ----
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+};
+
+struct FftPlan {
+  hipfftHandle h;
+  int64_t nu, nv;
+};
+
+struct PlanResult {
+  int64_t nruns = 0, ntiles = 0, nchunks = 0;
+  std::vector<int64_t> plane_chunk_off;  // chunk offset of each range: w plane group q (ngroups + 1), or the 2-D layer
+  int group = 1;                         // w planes per work unit (w-stacking plane groups)
+  uint64_t* runs = nullptr;
+  int64_t* run_goff = nullptr;
+  int64_t* tile_run_off = nullptr;
+  Chunk* chunks = nullptr;
+  void* perm = nullptr;  // bank-class ordered visibility stream (perm_encode entries), or NULL
+  bool phases = false;   // perm's entries carry row phases (RowMap::row_phase for the scatter)
+  uint32_t* dmask = nullptr;  // grid tiles the scatter writes, per plane (bit-packed, ntx / 32 words per tile row)
+};
+
+struct Workspace {
+  int device = 0;  // the device every buffer, stream and event belongs to
+  std::map<std::string, DevBuf> bufs;
+  std::vector<FftPlan> plans;
+  void* pinned = nullptr;  // small host staging
+  size_t pinned_bytes = 0;
+  std::vector<int64_t> corr_key;  // (npix_x, npix_y, nu, nv, W) of the cached cx / cy
+  std::vector<double> fw_key;     // (W, dw |nmin|) of the cached w-correction table
+  std::vector<int64_t> tw_ready;  // lengths whose FFT twiddle tables are on the device
+  // second stream: zeroes the first grid plane while the planner runs
+  hipStream_t side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool side_pending = false;
+  // the "grid" buffer when it is known all-zero (the masked FFT pass A zeroes
+  // what the scatter wrote), else NULL
+  double* grid_clean = nullptr;
+  // how many of its leading BYTES are known zero: a call on a smaller grid
+  // zeroes (and keeps clean) only its own planes' bytes, so the state is a byte
+  // count, not a plane count (a later larger-geometry call must not trust it)
+  size_t grid_clean_bytes = 0;
+  // CIP_ASYNC pipelining (cip_ms2dirty): consecutive calls alternate between
+  // two sets of planner buffers (parity; buf() appends the parity to buffer
+  // names while parity_scope is set), so the planner of call k + 1 runs on
+  // plan_stream beside call k's scatter and FFT; it only waits for
+  // call k - 1's work on the caller's stream (ev_done[parity]: its scatter
+  // read the plan, its FFT the masks and weight sum); the caller's stream
+  // waits for the plan (ev_planned). One plan stream per parity.
+  hipStream_t plan_stream = nullptr, plan_stream1 = nullptr;
+  hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_planned = nullptr, ev_entry = nullptr;
+  uint64_t call_seq = 0;
+  int parity = 0;
+  bool parity_scope = false;
+  // a planner ran on a caller's stream (parity-0 buffer names) since the last
+  // pipelined call: the next pipelined planner waits for that stream
+  bool plan_unscoped = false;
+  // the stream of the last CIP_ASYNC call, whose work may still be queued: a
+  // call on another stream first waits for it (the workspace is shared)
+  hipStream_t async_stream = nullptr;
+  // the last complete plan (its buffers stay untouched until the next planner
+  // runs) and the geometry it was made for: CIP_REUSE_PLAN calls with the
+  // same key grid through it. Cleared when a planner starts; never set for
+  // ragged rows (their row map lives in per-call buffers).
+  bool saved_valid = false;
+  std::vector<double> saved_key;
+  cip_gridder_params saved_p;
+  PlanResult saved_plan;
+};
+
+// ---- cip_workspace.hip ----
+void clear_error();
+// grow-only device buffer; returns nullptr (and sets the error) on failure
+void* buf_bytes(Workspace* ws, const char* name, size_t bytes);
+template <typename T>
+T* buf(Workspace* ws, const char* name, int64_t count) {
+  return (T*)buf_bytes(ws, name, (size_t)(count > 0 ? count : 1) * sizeof(T));
+}
+#define CIP_ALLOC(var, T, name, n)  \
+  T* var = buf<T>(ws, name, (n));   \
+  if (!var) return CIP_ENOMEM;
+// small pinned host staging; returns nullptr (and sets the error) on failure
+void* pinned(Workspace* ws, size_t bytes);
+int fft_plan(Workspace* ws, int64_t nu, int64_t nv, hipStream_t s, hipfftHandle* out);
+int fft_twiddles(Workspace* ws, int64_t n, hipStream_t s, double** out);
+int zero_on_side(Workspace* ws, void* p, size_t bytes, hipStream_t s);
+int join_side(Workspace* ws, hipStream_t s);
+
+// One entry-point call: its workspace and stream, and (profiled calls) the
+// event that starts span 5, the whole call.
+struct Call {
+  Workspace* ws = nullptr;
+  hipStream_t s = nullptr;
+  bool profiled = false;
+  hipEvent_t t0 = nullptr;
+};
+// Clears the thread's error, takes its workspace (which counts the call and
+// arms the reaper, so argument checks come first), waits for an earlier
+// CIP_ASYNC call on another stream; profiled: resets the profiler and marks
+// the start.
+int begin_call(void* hip_stream, bool profiled, Call* c);
+// Closes span 5 (profiled calls), synchronises the stream, reads the profile.
+int end_call(const Call& c);
+// the usual opening of an entry point, after its argument checks: declares
+// `call`, and `ws` and `s` as the bodies (and CIP_ALLOC) name them
+#define CIP_BEGIN_CALL(hip_stream, profiled)                                              \
+  Call call;                                                                              \
+  if (const int rc_ = begin_call(hip_stream, profiled, &call); rc_ != CIP_OK) return rc_; \
+  Workspace* const ws = call.ws;                                                          \
+  const hipStream_t s = call.s;                                                           \
+  (void)ws;
+
+// ---- cip_params.hip ----
+int choose(int64_t npix_x, int64_t npix_y, double px, double py, double epsilon, int support, int do_wstacking,
+           double wmin, double wmax, cip_gridder_params* out);
+GridGeometry geometry(const cip_gridder_params& p, double px, double py);
+int correction_vectors(Workspace* ws, const GridGeometry& g, int64_t npix_x, int64_t npix_y, hipStream_t s,
+                       double** cx_out, double** cy_out);
+int w_correction_table(Workspace* ws, const cip_gridder_params& prm, const GridGeometry& g, hipStream_t s,
+                       double** table, int64_t* n, double* dnu_out);
+int wstack_group(const GridGeometry& g, bool packed);
+bool grid_is_transposed(const GridGeometry& g, int64_t npix_x, int64_t npix_y);
+bool vis_dtype_ok(int d);
+bool public_dtypes(int vis_dtype, int wgt_dtype);
+int public_dtype_check(int vis_dtype, int wgt_dtype, bool any_vis);
+// the CIP_* switches (one table in cip_params.hip; place_rows64,
+// fft_f32_enabled and order_classes32 are declared in cip_internal.h)
+bool fft_pruned();
+bool grid_mask();
+bool scatter_order();
+bool packed_runs();
+bool ragged_pack();
+bool row_phases();
+int wstack_group_cap();
+int flush_store_mode();
+bool grid_f32_enabled();
+bool wacc_f32_enabled();
+bool fft_rowskip();
+
+struct Prepared {
+  cip_gridder_params p;
+  GridGeometry g;
+  double fixed_scale;
+  bool packed;  // single-precision class (CIP_ACC_SINGLE)
+  double* fx;
+  double* red;  // device [sum_w, max|wV|]
+  RowMap m;     // (row, channel) -> visibility index
+  PlanResult plan;
+};
+
+// Row slices of the ragged (tile) input layout: row r holds channels
+// [chan_start[r], chan_stop[r]) and the visibilities are concatenated in row
+// order (reference uvw_tiling/tile.py:83-115), nvis in total.
+struct RaggedRows {
+  const int32_t* chan_start;
+  const int32_t* chan_stop;
+  int64_t nvis;
+};
+
+// What prepare() plans for. given: fixed parameters (npix_x, npix_y and
+// epsilon are then not consulted); plane_end >= 0: a range of the w-plane stack.
+struct PlanRequest {
+  const double *uvw = nullptr, *freq = nullptr;
+  int64_t nrow = 0, nchan = 0;
+  const void *vis = nullptr, *wgt = nullptr;
+  int vis_dtype = CIP_C64, wgt_dtype = CIP_NONE;
+  const uint8_t* flags4 = nullptr;
+  int64_t npix_x = 0, npix_y = 0;
+  double px = 0.0, py = 0.0, epsilon = 0.0;
+  int support = 0, do_wstacking = 0;
+  bool packed = false;
+  const cip_gridder_params* given = nullptr;
+  const RaggedRows* ragged = nullptr;
+  bool reuse = false;      // CIP_REUSE_PLAN
+  bool want_group = true;  // w-plane groups (wstack_group); false: one plane per work unit
+  int64_t plane_begin = 0, plane_end = -1;
+};
+// cip_planner.hip. grid_out (may be NULL): also takes the workspace grid and
+// zeroes its first plane group on the side stream (the caller joins it)
+int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, double** grid_out = nullptr);
+
+// Correction vectors, FFT plan / twiddles and the pass-A buffer for one
+// (grid, image) geometry (cip_invert.hip dirty_stage)
+struct DirtyStage {
+  int64_t npix_x = 0, npix_y = 0;
+  double px = 0, py = 0;
+  bool fast = false;
+  hipfftHandle plan = nullptr;
+  double *tw_u = nullptr, *tw_v = nullptr, *fft_h = nullptr, *cx = nullptr, *cy = nullptr;
+};
+
+}  // namespace cip

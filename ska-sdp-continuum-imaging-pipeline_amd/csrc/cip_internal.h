@@ -21,6 +21,11 @@ int set_error(int code, const std::string& msg);
                                             hipGetErrorString(e_));            \
   } while (0)
 
+// ---- CIP_* switches the kernel units read (the table is in cip_params.hip;
+// fft_f32_enabled, CIP_FFT_F32, is declared with the FFT below) ----
+bool place_rows64();     // CIP_PLACE_ROWS64 (cip_plan.hip)
+bool order_classes32();  // CIP_ORDER_CLASSES (cip_grid.hip)
+
 // ---- scan (cip_plan.hip) -------------------------------------------------
 // In-place exclusive scan of n int64 values; tmp must hold scan_tmp_elems(n).
 int64_t scan_tmp_elems(int64_t n);

@@ -599,15 +599,6 @@ __device__ __forceinline__ void place_rows64_body(const double* __restrict__ uvw
   }
 }
 
-// CIP_PLACE_ROWS64=0: dense 64-channel rows through place_body (A/B)
-static bool place_rows64() {
-  static const bool on = [] {
-    const char* e = getenv("CIP_PLACE_ROWS64");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // The place pass (reduction fused, the place block = this workgroup); PLACE =
 // false: the reduction alone (CIP_REUSE_PLAN calls). RM = 3 / 4: dense rows of
 // a multiple of 64 channels through place_rows64_body (2-D / w-stacking).

@@ -19,7 +19,7 @@
 //  * strip_emit_kernel: the runs as Tile-layout row slices (uvw, channel
 //    range, MS row) and the strip's visibilities and weights gathered into
 //    slice order - the whole strip in one pass over the dense columns.
-#include "cip_internal.h"
+#include "cip_host.h"
 
 namespace cip {
 
@@ -284,3 +284,234 @@ hipError_t launch_strip_mask(const uint32_t* dmask, const GridGeometry& g, int64
 }
 
 }  // namespace cip
+
+// ------------------------------------------------------------ host API ----
+using namespace cip;
+
+extern "C" {
+
+// ---- the uv-strip split on the device (cip_strips.hip) ----
+static int strip_split_check(const cip_gridder_params* params, const double* uvw, int64_t nrow, const double* freq,
+                             int64_t nchan, GridGeometry* g) {
+  if (!params) return set_error(CIP_EINVAL, "params is NULL");
+  if (nrow < 0 || nchan < 1 || nchan > 65535) return set_error(CIP_EINVAL, "need nrow >= 0 and 1 <= nchan <= 65535");
+  if (nrow > 0 && (!uvw || !freq)) return set_error(CIP_EINVAL, "NULL uvw or freq");
+  const bool pow2 = params->nu > 0 && params->nv > 0 && (params->nu & (params->nu - 1)) == 0 &&
+                    (params->nv & (params->nv - 1)) == 0;
+  if (!pow2 || params->nv < 32 || params->nv > 16384)
+    return set_error(CIP_EINVAL, "strips need a power-of-two grid of 32 .. 16384 rows");
+  *g = geometry(*params, 1.0, 1.0);
+  return CIP_OK;
+}
+
+int cip_strip_histogram(const double* uvw, int64_t nrow, const double* freq, int64_t nchan,
+                        const cip_gridder_params* params, double pixsize_x, double pixsize_y, void* hip_stream,
+                        int64_t* hist) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_split_check(params, uvw, nrow, freq, nchan, &g); rc != CIP_OK) return rc;
+  if (!hist) return set_error(CIP_EINVAL, "NULL hist");
+  g = geometry(*params, pixsize_x, pixsize_y);
+  CIP_BEGIN_CALL(hip_stream, false)
+  if (nrow == 0) {
+    CIP_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(int64_t) * 2 * g.nv, s));
+    return CIP_OK;
+  }
+  CIP_ALLOC(fx, double, "strip_fx", nchan)
+  CIP_HIP_CHECK(launch_freq_scale(freq, nchan, fx, nullptr, s));
+  const int nb = strip_hist_blocks(nrow);
+  CIP_ALLOC(partial, uint32_t, "strip_hist_partial", (int64_t)nb * 2 * g.nv)
+  CIP_HIP_CHECK(launch_strip_hist(uvw, nrow, fx, nchan, g, partial, nb, hist, s));
+  return CIP_OK;
+}
+
+int cip_strip_split(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const void* vis,
+                    int vis_dtype, const void* wgt, int wgt_dtype, const cip_gridder_params* params, double pixsize_y,
+                    int64_t y0, int64_t y1, void* hip_stream, int64_t* counts, double* slice_uvw,
+                    int32_t* chan_start, int32_t* chan_stop, int64_t* slice_row, void* vis_out, void* wgt_out) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_split_check(params, uvw, nrow, freq, nchan, &g); rc != CIP_OK) return rc;
+  g = geometry(*params, 1.0, pixsize_y);
+  if (!counts) return set_error(CIP_EINVAL, "NULL counts");
+  if (y0 < 0 || y1 > g.nv || y1 <= y0) return set_error(CIP_EINVAL, "strip rows outside the grid");
+  const int vb = vis ? (vis_dtype == CIP_C64 ? 8 : (vis_dtype == CIP_C128 ? 16 : -1)) : 0;
+  const int wb = (vis && wgt) ? (wgt_dtype == CIP_F32 ? 4 : (wgt_dtype == CIP_F64 ? 8 : -1)) : 0;
+  if (vb < 0) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
+  if (wb < 0) return set_error(CIP_EINVAL, "wgt dtype must be float32 or float64");
+  CIP_BEGIN_CALL(hip_stream, false)
+  CIP_ALLOC(fx, double, "strip_fx", nchan)
+  CIP_ALLOC(row_runs, int64_t, "strip_row_runs", nrow + 1)
+  CIP_ALLOC(row_vis, int64_t, "strip_row_vis", nrow + 1)
+  CIP_ALLOC(scan_tmp, int64_t, "strip_scan_tmp", scan_tmp_elems(nrow + 1))
+  CIP_HIP_CHECK(launch_freq_scale(freq, nchan, fx, nullptr, s));
+  // the counts and their scans: phase 1 (slice_uvw == NULL) reports the totals;
+  // phase 2 recounts (the same arithmetic, the same numbers) and emits
+  CIP_HIP_CHECK(launch_strip_count(uvw, nrow, fx, nchan, g, y0, y1, row_runs, row_vis, s));
+  CIP_HIP_CHECK(exclusive_scan_i64(row_runs, nrow + 1, scan_tmp, s));
+  CIP_HIP_CHECK(exclusive_scan_i64(row_vis, nrow + 1, scan_tmp, s));
+  if (!slice_uvw) {
+    int64_t* h = (int64_t*)pinned(ws, 2 * sizeof(int64_t));
+    if (!h) return CIP_ENOMEM;
+    CIP_HIP_CHECK(hipMemcpyAsync(&h[0], row_runs + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    CIP_HIP_CHECK(hipMemcpyAsync(&h[1], row_vis + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    counts[0] = h[0];
+    counts[1] = h[1];
+    return CIP_OK;
+  }
+  if (!chan_start || !chan_stop || !slice_row) return set_error(CIP_EINVAL, "NULL slice outputs");
+  if (vb > 0 && !vis_out) return set_error(CIP_EINVAL, "NULL vis_out");
+  if (wb > 0 && !wgt_out) return set_error(CIP_EINVAL, "NULL wgt_out");
+  if (nrow > 0)
+    CIP_HIP_CHECK(launch_strip_emit(uvw, nrow, fx, nchan, g, y0, y1, row_runs, row_vis, vis, vb, wgt, wb, slice_uvw,
+                                    chan_start, chan_stop, slice_row, vb ? vis_out : nullptr, wb ? wgt_out : nullptr,
+                                    s));
+  return CIP_OK;
+}
+
+// strips of the pruned FFT (multi-GPU strong scaling)
+static int strip_check(const cip_gridder_params* params, int64_t npix_x, int64_t npix_y, GridGeometry* g) {
+  if (!params) return set_error(CIP_EINVAL, "params is NULL");
+  *g = geometry(*params, 1.0, 1.0);
+  if (!grid_is_transposed(*g, npix_x, npix_y))
+    return set_error(CIP_EINVAL, "strips need the pruned-FFT grid layout (power-of-two grids, cip_grid_layout == 1)");
+  return CIP_OK;
+}
+
+// pass A of a strip, after the caller's own checks: rows [y0, y1) of the
+// buffer into H; dmask / row0 / row_slot / nlive as launch_fft_rows_strip
+static int strip_rows(void* hip_stream, double* grid, const GridGeometry& g, int64_t npix_x, int64_t y0, int64_t y1,
+                      double* H, const uint32_t* dmask = nullptr, int64_t row0 = 0,
+                      const int64_t* row_slot = nullptr, int64_t nlive = 0) {
+  CIP_BEGIN_CALL(hip_stream, false)
+  double* tw_u = nullptr;
+  if (const int rc = fft_twiddles(ws, g.nu, s, &tw_u); rc != CIP_OK) return rc;
+  CIP_HIP_CHECK(launch_fft_rows_strip(grid, g.nu, g.nv, npix_x, tw_u, y0, y1, H, s, dmask, row0, row_slot, nlive));
+  return end_call(call);
+}
+
+// [i0, i1): image rows of a strip's pass B, whole column blocks of 4
+static int strip_cols_range_check(int64_t i0, int64_t i1, int64_t npix_x) {
+  if (i0 < 0 || i1 > npix_x || i1 <= i0 || i0 % 4 || i1 % 4)
+    return set_error(CIP_EINVAL, "image row range must be multiples of 4 inside [0, npix_x]");
+  return CIP_OK;
+}
+
+int cip_strip_rows(double* grid, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y, int64_t y0,
+                   int64_t y1, void* hip_stream, double* H) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (!grid || !H) return set_error(CIP_EINVAL, "NULL grid or H");
+  if (y0 < 0 || y1 > g.nv || y1 <= y0) return set_error(CIP_EINVAL, "row range outside the grid");
+  return strip_rows(hip_stream, grid, g, npix_x, y0, y1, H);
+}
+
+int cip_strip_rows_masked(double* grid, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y,
+                          int64_t y0, int64_t y1, int64_t row0, const uint32_t* tile_bits, void* hip_stream,
+                          double* H) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (!grid || !H || !tile_bits) return set_error(CIP_EINVAL, "NULL grid, H or tile_bits");
+  if (y0 < 0 || y1 > g.nv || y1 <= y0) return set_error(CIP_EINVAL, "row range outside the grid");
+  if (row0 < 0 || row0 >= g.nv) return set_error(CIP_EINVAL, "row0 outside the grid");
+  if (g.ntx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
+  return strip_rows(hip_stream, grid, g, npix_x, y0, y1, H, tile_bits, row0);
+}
+
+int cip_strip_rows_packed(double* grid, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y,
+                          int64_t y0, int64_t y1, int64_t row0, const uint32_t* tile_bits, const int64_t* row_slot,
+                          int64_t nlive, void* hip_stream, double* H) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (!grid || !tile_bits || !row_slot) return set_error(CIP_EINVAL, "NULL grid, tile_bits or row_slot");
+  if (y0 < 0 || y1 > g.nv || y1 <= y0) return set_error(CIP_EINVAL, "row range outside the grid");
+  if (row0 < 0 || row0 >= g.nv) return set_error(CIP_EINVAL, "row0 outside the grid");
+  if (nlive < 0 || nlive > y1 - y0) return set_error(CIP_EINVAL, "nlive outside [0, y1 - y0]");
+  if (nlive > 0 && !H) return set_error(CIP_EINVAL, "NULL H");
+  if (g.ntx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
+  return strip_rows(hip_stream, grid, g, npix_x, y0, y1, H, tile_bits, row0, row_slot, nlive);
+}
+
+int cip_strip_cols(const double* H, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y, int64_t i0,
+                   int64_t i1, const double* norm, void* hip_stream, double* dirty_rows) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (params->do_wstacking)
+    return set_error(CIP_EINVAL, "cip_strip_cols: 2-D grids only (w-stacking strips use cip_strip_cols_wplane + "
+                                 "cip_strip_wfinal)");
+  if (!H || !dirty_rows) return set_error(CIP_EINVAL, "NULL H or dirty_rows");
+  if (const int rc = strip_cols_range_check(i0, i1, npix_x); rc != CIP_OK) return rc;
+  CIP_BEGIN_CALL(hip_stream, false)
+  double *tw_v = nullptr, *cx = nullptr, *cy = nullptr;
+  if (const int rc = fft_twiddles(ws, g.nv, s, &tw_v); rc != CIP_OK) return rc;
+  if (const int rc = correction_vectors(ws, g, npix_x, npix_y, s, &cx, &cy); rc != CIP_OK) return rc;
+  CIP_HIP_CHECK(launch_fft_cols_strip(H, g.nv, npix_x, npix_y, tw_v, i0, i1, dirty_rows, cx, cy, norm, s));
+  return end_call(call);
+}
+
+int cip_strip_pack_rows(const void* H, int64_t nb, int64_t h, int elem_bytes, const int64_t* slot, int64_t nlive,
+                        void* hip_stream, void* out) {
+  clear_error();
+  if (elem_bytes != 8 && elem_bytes != 16) return set_error(CIP_EINVAL, "elem_bytes must be 8 or 16");
+  if (nb < 0 || h < 0 || nlive < 0 || nlive > h) return set_error(CIP_EINVAL, "bad pack sizes");
+  if (nb > 65535) return set_error(CIP_EINVAL, "more than 65535 column blocks");
+  if (nb * h * nlive > 0 && (!H || !slot || !out)) return set_error(CIP_EINVAL, "NULL pointer");
+  CIP_HIP_CHECK(launch_strip_pack(H, nb, h, elem_bytes / 4, slot, nlive, out, (hipStream_t)hip_stream));
+  return CIP_OK;
+}
+
+int cip_strip_unpack_rows(const void* recv, int64_t nb, int64_t nv, int elem_bytes, const int64_t* rec,
+                          const int64_t* stride, void* hip_stream, void* H) {
+  clear_error();
+  if (elem_bytes != 8 && elem_bytes != 16) return set_error(CIP_EINVAL, "elem_bytes must be 8 or 16");
+  if (nb < 0 || nv < 0) return set_error(CIP_EINVAL, "bad unpack sizes");
+  if (nb > 65535) return set_error(CIP_EINVAL, "more than 65535 column blocks");
+  if (nb * nv > 0 && (!rec || !stride || !H)) return set_error(CIP_EINVAL, "NULL pointer");
+  CIP_HIP_CHECK(launch_strip_unpack(recv, nb, nv, elem_bytes / 4, rec, stride, H, (hipStream_t)hip_stream));
+  return CIP_OK;
+}
+
+int cip_strip_cols_wplane(const double* H, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y,
+                          double pixsize_x, double pixsize_y, int64_t i0, int64_t i1, int64_t plane, int first,
+                          void* hip_stream, double* acc_rows) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (!params->do_wstacking) return set_error(CIP_EINVAL, "cip_strip_cols_wplane: w-stacking parameters only");
+  if (!H || !acc_rows) return set_error(CIP_EINVAL, "NULL H or acc_rows");
+  if (plane < 0 || plane >= params->nplanes) return set_error(CIP_EINVAL, "plane out of range");
+  if (const int rc = strip_cols_range_check(i0, i1, npix_x); rc != CIP_OK) return rc;
+  CIP_BEGIN_CALL(hip_stream, false)
+  double* tw_v = nullptr;
+  if (const int rc = fft_twiddles(ws, g.nv, s, &tw_v); rc != CIP_OK) return rc;
+  CIP_HIP_CHECK(launch_fft_cols_strip_wplane(H, g.nv, npix_x, npix_y, tw_v, i0, i1, acc_rows, pixsize_x, pixsize_y,
+                                             params->w0 + (double)plane * params->dw, first != 0, s));
+  return end_call(call);
+}
+
+int cip_strip_wfinal(double* acc_rows, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y,
+                     double pixsize_x, double pixsize_y, int64_t i0, int64_t i1, const double* norm,
+                     void* hip_stream) {
+  clear_error();
+  GridGeometry g;
+  if (const int rc = strip_check(params, npix_x, npix_y, &g); rc != CIP_OK) return rc;
+  if (!params->do_wstacking) return set_error(CIP_EINVAL, "cip_strip_wfinal: w-stacking parameters only");
+  if (!acc_rows) return set_error(CIP_EINVAL, "NULL acc_rows");
+  if (i0 < 0 || i1 > npix_x || i1 <= i0) return set_error(CIP_EINVAL, "image rows outside [0, npix_x)");
+  CIP_BEGIN_CALL(hip_stream, false)
+  double *cx = nullptr, *cy = nullptr, *fwd = nullptr;
+  int64_t fw_n = 0;
+  double dnu = 0.0;
+  if (const int rc = correction_vectors(ws, g, npix_x, npix_y, s, &cx, &cy); rc != CIP_OK) return rc;
+  if (const int rc = w_correction_table(ws, *params, g, s, &fwd, &fw_n, &dnu); rc != CIP_OK) return rc;
+  CIP_HIP_CHECK(launch_wfinal_correct(acc_rows, npix_x, npix_y, pixsize_x, pixsize_y, cx, cy, fwd, fw_n, dnu, g.dw, s,
+                                      i0, i1 - i0, norm));
+  return end_call(call);
+}
+
+}  // extern "C"

@@ -10,7 +10,7 @@
 // bisection (tiling_plan.py:150-181): keys are monotone in frequency, so the
 // maximal constant runs are the same set, found here by one linear pass per
 // row on the device.
-#include "cip_internal.h"
+#include "cip_host.h"
 
 namespace cip {
 
@@ -201,3 +201,104 @@ hipError_t launch_facet_rephase(const double* uvw, int64_t nrow, const double* f
 }
 
 }  // namespace cip
+
+// ------------------------------------------------------------ host API ----
+using namespace cip;
+
+extern "C" {
+
+int cip_tile_runs(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const double* tile_size3,
+                  int64_t row_offset, void* hip_stream, int64_t* n_runs, int64_t* run_key, int64_t* run_row,
+                  int32_t* run_c0, int32_t* run_c1) {
+  clear_error();
+  if (!tile_size3 || !n_runs) return set_error(CIP_EINVAL, "NULL tile_size or n_runs");
+  if (nrow < 0 || nchan < 1) return set_error(CIP_EINVAL, "need nrow >= 0 and nchan >= 1");
+  CIP_BEGIN_CALL(hip_stream, false)
+  if (nrow == 0) {
+    *n_runs = 0;
+    return CIP_OK;
+  }
+  CIP_ALLOC(winv, double, "winv", nchan)
+  CIP_ALLOC(row_runs, int64_t, "row_runs", nrow + 1)
+  CIP_ALLOC(tmp, int64_t, "scan_tmp_rows", scan_tmp_elems(nrow + 1))
+  CIP_HIP_CHECK(launch_wavelength_inv(freq, nchan, winv, s));
+  CIP_HIP_CHECK(hipMemsetAsync(row_runs + nrow, 0, sizeof(int64_t), s));
+  CIP_HIP_CHECK(launch_tile_run_count(uvw, nrow, winv, nchan, tile_size3[0], tile_size3[1], tile_size3[2], row_runs,
+                                      s));
+  CIP_HIP_CHECK(exclusive_scan_i64(row_runs, nrow + 1, tmp, s));
+  int64_t* h = (int64_t*)pinned(ws, sizeof(int64_t));
+  if (!h) return CIP_ENOMEM;
+  CIP_HIP_CHECK(hipMemcpyAsync(h, row_runs + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  const int64_t total = h[0];
+  if (run_key == nullptr) {
+    *n_runs = total;
+    return CIP_OK;
+  }
+  if (*n_runs < total) return set_error(CIP_EINVAL, "output buffers too small (pass *n_runs = capacity)");
+  if (!run_row || !run_c0 || !run_c1) return set_error(CIP_EINVAL, "NULL output buffer");
+  CIP_HIP_CHECK(launch_tile_run_emit(uvw, nrow, winv, nchan, tile_size3[0], tile_size3[1], tile_size3[2],
+                                     row_offset, row_runs, run_key, run_row, run_c0, run_c1, s));
+  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  *n_runs = total;
+  return CIP_OK;
+}
+
+int cip_stokes(const void* vis4, const uint8_t* flags4, const float* wgt4, int64_t n, int stokes, void* hip_stream,
+               void* vis_out, uint8_t* flag_out, float* wgt_out, float* eff_w) {
+  clear_error();
+  if (n < 0) return set_error(CIP_EINVAL, "n must be >= 0");
+  if (stokes < CIP_STOKES_I || stokes > CIP_STOKES_V) return set_error(CIP_EINVAL, "stokes must be I, Q, U or V");
+  if (n == 0) return CIP_OK;
+  if (vis_out && !vis4) return set_error(CIP_EINVAL, "visibilities requested without vis4");
+  if ((wgt_out || eff_w) && !wgt4) return set_error(CIP_EINVAL, "weights requested without wgt4");
+  if ((flag_out || eff_w) && !flags4) return set_error(CIP_EINVAL, "flags requested without flags4");
+  hipStream_t s = (hipStream_t)hip_stream;
+  CIP_HIP_CHECK(launch_stokes(stokes, vis4, flags4, wgt4, n, vis_out, flag_out, wgt_out, eff_w, s));
+  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  return CIP_OK;
+}
+
+int cip_stokes_i(const void* vis4, const uint8_t* flags4, const float* wgt4, int64_t n, void* hip_stream,
+                 void* vis_i, uint8_t* flag_i, float* wgt_i, float* eff_w) {
+  return cip_stokes(vis4, flags4, wgt4, n, CIP_STOKES_I, hip_stream, vis_i, flag_i, wgt_i, eff_w);
+}
+
+int cip_facet_rephase(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const void* vis,
+                      int vis_dtype, double l0, double m0, void* hip_stream, double* uvw_out, void* vis_out) {
+  clear_error();
+  if (nrow < 0 || nchan < 1) return set_error(CIP_EINVAL, "need nrow >= 0 and nchan >= 1");
+  if (!vis_dtype_ok(vis_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
+  if (!(l0 * l0 + m0 * m0 < 1.0)) return set_error(CIP_EINVAL, "facet centre outside the unit circle");
+  if (nrow == 0) return CIP_OK;
+  if (!uvw || !freq || !uvw_out || (vis_out && !vis)) return set_error(CIP_EINVAL, "NULL pointer");
+  CIP_BEGIN_CALL(hip_stream, false)
+  CIP_ALLOC(delay, double, "facet_delay", nrow)
+  // Q: the minimal rotation taking z = (0, 0, 1) to s0 (Rodrigues about z x s0)
+  const double n0 = std::sqrt(1.0 - l0 * l0 - m0 * m0);
+  const double kx = -m0, ky = l0;  // z x s0 (unnormalised; |k| = sin theta)
+  const double sn2 = kx * kx + ky * ky, c = n0;
+  double Q[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (sn2 > 0.0) {
+    const double f = (1.0 - c) / sn2;  // (1 - cos) / sin^2 on the unnormalised axis
+    // Q = I + [k]x + f [k]x^2, [k]x = ((0, 0, ky), (0, 0, -kx), (-ky, kx, 0))
+    Q[0] = 1.0 - f * ky * ky;
+    Q[1] = f * kx * ky;
+    Q[2] = ky;
+    Q[3] = f * kx * ky;
+    Q[4] = 1.0 - f * kx * kx;
+    Q[5] = -kx;
+    Q[6] = -ky;
+    Q[7] = kx;
+    Q[8] = 1.0 - f * sn2;
+  }
+  double qt[9];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) qt[3 * a + b] = Q[3 * b + a];
+  CIP_HIP_CHECK(launch_facet_rephase(uvw, nrow, freq, nchan, vis_out ? vis : nullptr, vis_dtype == CIP_C128, qt, l0, m0,
+                                     uvw_out, delay, vis_out, s));
+  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  return CIP_OK;
+}
+
+}  // extern "C"

@@ -30,7 +30,7 @@ from .measurement_set import (  # noqa: E402
 
 # Load libcip_hip.so at import, on the importing thread, when it is built: the
 # library records the thread that loads it as the main thread (whose workspaces
-# are left to process teardown, cip_api.hip), so the first call from a worker
+# are left to process teardown, cip_workspace.hip), so the first call from a worker
 # thread must not be the one that loads it. A missing library raises at the
 # first call instead (no CPU fallback).
 try:

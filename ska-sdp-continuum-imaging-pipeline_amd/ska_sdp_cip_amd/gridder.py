@@ -171,6 +171,17 @@ def _check_device_tensor(t, device, what):
         raise ValueError(f"{what}: tensor on {t.device}, expected {device}")
 
 
+def _invert_flags(do_wstacking, single, psf, normalise, synchronize, resident_inputs, reuse_plan):
+    """The CIP_* flag word of a cip_ms2dirty* call."""
+    return ((_lib.CIP_WSTACKING if do_wstacking else 0)
+            | (_lib.CIP_ACC_SINGLE if single else 0)
+            | (_lib.CIP_PSF if psf else 0)
+            | (_lib.CIP_NORMALISE if normalise else 0)
+            | (0 if synchronize else _lib.CIP_ASYNC)
+            | (_lib.CIP_PIPELINE if resident_inputs else 0)
+            | (_lib.CIP_REUSE_PLAN if reuse_plan else 0))
+
+
 def _ms2dirty_call(uvw, freq, vis, wgt, vis_codes, wgt_codes, npix_x, npix_y, pixsize_x, pixsize_y, epsilon,
                    support, do_wstacking, single_precision_accumulation, psf, normalise, stream, out,
                    sum_weights, params, synchronize=True, resident_inputs=False, reuse_plan=False, planes=None):
@@ -182,13 +193,8 @@ def _ms2dirty_call(uvw, freq, vis, wgt, vis_codes, wgt_codes, npix_x, npix_y, pi
             wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
             int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y), float(epsilon),
             int(support or 0),
-            (_lib.CIP_WSTACKING if do_wstacking else 0)
-            | (_lib.CIP_ACC_SINGLE if single_precision_accumulation else 0)
-            | (_lib.CIP_PSF if psf else 0)
-            | (_lib.CIP_NORMALISE if normalise else 0)
-            | (0 if synchronize else _lib.CIP_ASYNC)
-            | (_lib.CIP_PIPELINE if resident_inputs else 0)
-            | (_lib.CIP_REUSE_PLAN if reuse_plan else 0))
+            _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
+                          reuse_plan))
     tail = (stream, out.data_ptr(), sum_weights.data_ptr() if sum_weights is not None else None, params)
     if planes is not None:
         return _lib.lib().cip_ms2dirty_wplanes(*head, int(planes[0]), int(planes[1]), *tail)
@@ -267,13 +273,8 @@ def device_ms2dirty_stokes_i(
             uvw.data_ptr(), nrow, freq.data_ptr(), nchan, None if vis4 is None else vis4.data_ptr(),
             None if flags4 is None else flags4.data_ptr(), wgt4.data_ptr(), int(npix_x), int(npix_y),
             float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
-            (_lib.CIP_WSTACKING if do_wstacking else 0)
-            | (_lib.CIP_ACC_SINGLE if single_precision_accumulation else 0)
-            | (_lib.CIP_PSF if psf else 0)
-            | (_lib.CIP_NORMALISE if normalise else 0)
-            | (0 if synchronize else _lib.CIP_ASYNC)
-            | (_lib.CIP_PIPELINE if resident_inputs else 0)
-            | (_lib.CIP_REUSE_PLAN if reuse_plan else 0),
+            _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
+                          reuse_plan),
             stream, out.data_ptr(), sum_weights.data_ptr() if sum_weights is not None else None, params)
     _lib.check(rc)
     return out, params

@@ -2,7 +2,7 @@
 Hard limits of the C ABI (include/cip.h): nchan <= 65535 (the run record's
 16-bit channel fields), and the planner's fallback above 2^32 visibilities
 (the bank-class order needs a 32-bit flattened index; larger inputs grid in
-plain tile order, cip_api.hip make_plan) - checked by linearity: the image of
+plain tile order, cip_planner.hip make_plan) - checked by linearity: the image of
 4,295,032,830 visibilities (fallback) equals the sum of the images of its two
 row halves (each < 2^32, ordered path).
 """

@@ -11,8 +11,9 @@ process) up to the order of the flush's global adds.
 Cases (the flush-store and dense-row place tests' builders): cip_ms2dirty in
 2-D on the fp64 class (complex64 / complex128 input, 64 / 192 / 256
 channels), the reference's w-stacking call (packed class, plane groups), the
-PSF, repeated calls, the uv-strip path over ragged row slices (no phases:
-their entries are 64-bit) and the chunked accumulating gridder. Weight sums
+PSF, repeated calls, the uv-strip path over ragged row slices (their 64-bit
+entries carry the phase in bit 63; like every case here it compares phases on
+against phases off) and the chunked accumulating gridder. Weight sums
 and the run / work-unit counts must be equal bit for bit.
 """
 

@@ -1,6 +1,6 @@
 """
 The packed class's w-stacking float plane accumulator (CIP_WACC_F32, default
-on; cip_api.hip ms2dirty_impl, cip_fft.hip fft_cols_kernel<.., float>) against
+on; cip_invert.hip ms2dirty_impl, cip_fft.hip fft_cols_kernel<.., float>) against
 the fp64-accumulated image, and the fp64 transforms (CIP_FFT_F32=0), with
 which the float accumulator must stay off (the fp64-output pass B
 would write doubles across the float buffer). Each mode runs in a child

@@ -1,6 +1,6 @@
 """
 The per-thread workspace's kept-clean grid across calls of different
-geometries (cip_api.hip grid_clean_bytes): a call on a smaller
+geometries (cip_host.h Workspace::grid_clean_bytes): a call on a smaller
 power-of-two grid zeroes and keeps clean only ITS bytes of the reused grid
 buffer, so a later call on a larger grid must not trust the rest. Sequence:
 non-power-of-two grid (hipFFT path, leaves the buffer dirty) -> small

@@ -177,7 +177,7 @@ def test_params_match_oracle():
 
 
 def test_plane_group_and_wplane_split_on_its_lattice(monkeypatch):
-    # cip_plane_group is the scatter's w-plane group (cip_api.hip wstack_group):
+    # cip_plane_group is the scatter's w-plane group (cip_params.hip wstack_group):
     # 1 in 2-D and above W = 16, 7 packed at W = 6 (6 at W = 8), 3 / 2 in the fp64 class;
     # split_planes with that group cuts only on group boundaries
     from ska_sdp_cip_amd import wplanes
@@ -196,6 +196,36 @@ def test_plane_group_and_wplane_split_on_its_lattice(monkeypatch):
     split = wplanes.split_planes(np.ones(pw.nplanes), 3, group=g)
     assert split[0][0] == 0 and split[-1][1] == pw.nplanes
     assert all(a % g == 0 or a == pw.nplanes for a, _ in split[1:])
+
+
+_LAYOUT_CHILD = """
+import ctypes, importlib.util
+spec = importlib.util.spec_from_file_location("cip_lib", {lib_py!r})
+m = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(m)
+p = m.choose_params(512, 512, 1e-5, 1e-5, 1e-4)
+assert (p.nu, p.nv) == (1024, 1024), (p.nu, p.nv)
+print(m.lib().cip_grid_layout(ctypes.byref(p), 512, 512))
+"""
+
+
+def test_fft_pruned_switch_is_read_by_grid_layout():
+    # the boolean form of the switch table (cip_params.hip): CIP_FFT_PRUNED is read
+    # once per process, so each value gets a fresh one; a 1024 x 1024 grid (the
+    # smallest length cip_fft.hip fast_fft_supported takes) with a 512 x 512 image
+    # has the pruned FFT's layout unless the switch's first character is '0'
+    import os
+    import subprocess
+    import sys
+
+    child = _LAYOUT_CHILD.format(lib_py=str(Path(_lib.__file__)))
+    for value, layout in [(None, 1), ("1", 1), ("0", 0)]:
+        env = {k: v for k, v in os.environ.items() if k != "CIP_FFT_PRUNED"}
+        if value is not None:
+            env["CIP_FFT_PRUNED"] = value
+        r = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        assert int(r.stdout.strip()) == layout, value
 
 
 def test_library_exports_every_declared_symbol():

@@ -2,7 +2,7 @@
 The oracle pipeline (gridding + FFT + correction [+ w-stacking]) against the
 fp64 direct DFT that defines ms2dirty, for every supported kernel support: the
 measured accuracy is the table behind the epsilon -> support choice
-(cip_api.hip support_for_epsilon, oracle.support_for_epsilon).
+(cip_params.hip support_for_epsilon, oracle.support_for_epsilon).
 """
 import numpy as np
 import pytest
