@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cip_dispatch.h"
 #include "es_kernels.h"
 
 #define CIP_SPEED_OF_LIGHT 299792458.0
@@ -67,7 +68,8 @@ __host__ __device__ inline int64_t floor_div(int64_t a, int64_t b) {
   return (q * b > a) ? q - 1 : q;
 }
 
-// Horner evaluation of the even/odd halves of piece k at z = y^2.
+// Horner evaluation of the even/odd halves of piece k at z = y^2 (one
+// EsKernel per entry of LaneSupports, cip_dispatch.h).
 template <int W>
 struct EsKernel;
 
@@ -508,6 +510,12 @@ __device__ __forceinline__ int64_t ragged_row_of(const RowMap& m, int64_t s, int
 // visibilities over 3.9M rows x 256 channels take 30 + 22 + 8 bits), so the
 // scatter needs neither a row lookup nor the delta[row] gather; else (row <<
 // 16) | channel and index = delta[row] + channel.
+// bits that hold every value below n (the field widths above; at least 1)
+inline int index_bits(int64_t n) {
+  int b = 1;
+  while (b < 62 && ((int64_t)1 << b) < n) ++b;
+  return b;
+}
 __device__ __forceinline__ uint64_t perm_entry(const void* perm, const RowMap& m, int64_t q) {
   return m.delta ? ((const uint64_t*)perm)[q] : (uint64_t)((const uint32_t*)perm)[q];
 }
@@ -577,18 +585,16 @@ __device__ __forceinline__ void tile_origin(int64_t key, const GridGeometry& g, 
   *Y0 = ((t / g.ntx) % g.nty) * kTile;
 }
 
-// visibility / weight loads by dtype (CIP_C64 -> float2, CIP_C128 -> double2;
-// raw linear-feed columns -> Pol4 + WK_POL4I, Stokes I formed on load)
-enum { WK_NONE = 0, WK_F32 = 1, WK_F64 = 2, WK_POL4I = 3 };
-// internal vis / wgt dtype code of the raw linear-feed input (not in cip.h:
-// reached through cip_ms2dirty_stokes_i only)
-constexpr int CIP_POL4I = 0x100;
-
 // One visibility's linear-feed correlations (XX, XY, YX, YY) in complex64:
 // the raw (nrow, nchan, 4) MS column (cip_ms2dirty_stokes_i).
 struct Pol4 {
   float2 c[4];
 };
+// (visibility dtype, weight dtype) -> f(type_tag<VisT>{}, int_tag<WK>{}) (cip_dispatch.h)
+template <typename F>
+auto dispatch_vis_wgt(int vis_dtype, int wgt_dtype, F&& f) {
+  return dispatch_vis_wgt<float2, double2, Pol4>(vis_dtype, wgt_dtype, std::forward<F>(f));
+}
 
 // Stokes I of the raw columns in the reference's numpy float32 arithmetic
 // (invert.py:86-116, :72-76; bit-identical to cip_stokes_i, cip_tiling.hip):

@@ -215,24 +215,20 @@ __global__ __launch_bounds__(kDegridThreads) void degrid_kernel(
 
 // group: w planes per work unit (the plan's: 1 in 2-D, 1 .. 3 in w-stacking)
 template <int W>
-hipError_t launch_degrid_w(int group, dim3 gd, hipStream_t s, const double* uvw, const double* fx, const RowMap& m,
-                           const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t cb,
-                           const GridGeometry& g, int64_t plane, const double* planes, const DegridOut& o) {
-#define LAUNCH(WSV, GG)                                                                                          \
-  degrid_kernel<W, WSV, GG><<<gd, dim3(kDegridThreads), 0, s>>>(uvw, fx, m, runs, run_goff, chunks, cb, g, plane, \
-                                                                 (const double2*)planes, o)
-  if (!g.do_wstacking) {
-    if (group != 1 || o.acc) return hipErrorInvalidValue;
-    LAUNCH(false, 1);
-  } else {
-    if (!o.acc) return hipErrorInvalidValue;
-    if (group == 1) LAUNCH(true, 1);
-    else if (group == 2) LAUNCH(true, 2);
-    else if (group == 3) LAUNCH(true, 3);
-    else return hipErrorInvalidValue;
+hipError_t launch_degrid_w(const DegridLaunch& a, dim3 gd, hipStream_t s) {
+  const PlanView& p = a.plan;
+  auto launch = [&](auto wstack, auto group) {
+    degrid_kernel<W, decltype(wstack)::value, decltype(group)::value><<<gd, dim3(kDegridThreads), 0, s>>>(
+        p.uvw, p.fx, p.m, p.runs, p.run_goff, p.chunks, a.chunk_begin, a.g, a.plane, (const double2*)a.planes, a.out);
+    return hipGetLastError();
+  };
+  if (!a.g.do_wstacking) {
+    if (a.group != 1 || a.out.acc) return hipErrorInvalidValue;
+    return launch(std::false_type{}, int_tag<1>{});
   }
-#undef LAUNCH
-  return hipGetLastError();
+  if (!a.out.acc) return hipErrorInvalidValue;
+  return dispatch_int<1, 2, 3>(a.group, hipErrorInvalidValue,
+                               [&](auto group) { return launch(std::true_type{}, group); });
 }
 
 }  // namespace cip

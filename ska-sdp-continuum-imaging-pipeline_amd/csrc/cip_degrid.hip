@@ -84,28 +84,12 @@ hipError_t launch_degrid_pad(const double* image, int64_t npix_x, int64_t npix_y
   return hipGetLastError();
 }
 
-hipError_t launch_degrid(int support, int group, const double* uvw, const double* fx, const RowMap& m,
-                         const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t chunk_begin,
-                         int64_t nchunks, const GridGeometry& g, int64_t plane, const double* planes,
-                         const DegridOut& o, hipStream_t s) {
-  if (nchunks <= 0) return hipSuccess;
-  if (m.delta != nullptr) return hipErrorInvalidValue;  // dense MS rows only
-  const dim3 gd((unsigned)nchunks);
-#define CASE(WW) \
-  case WW:       \
-    return launch_degrid_w<WW>(group, gd, s, uvw, fx, m, runs, run_goff, chunks, chunk_begin, g, plane, planes, o);
-  switch (support) {
-    CASE(4)
-    CASE(6)
-    CASE(8)
-    CASE(10)
-    CASE(12)
-    CASE(14)
-    CASE(16)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef CASE
+hipError_t launch_degrid(const DegridLaunch& a, hipStream_t s) {
+  if (a.nchunks <= 0) return hipSuccess;
+  if (a.plan.m.delta != nullptr) return hipErrorInvalidValue;  // dense MS rows only
+  const dim3 gd((unsigned)a.nchunks);
+  return dispatch_int(LaneSupports{}, a.support, hipErrorInvalidValue,
+                      [&](auto w) { return launch_degrid_w<decltype(w)::value>(a, gd, s); });
 }
 
 // vis_io[i] = wt acc[i] (an exact 0 for a zero weight) or vis_io[i] -= wt

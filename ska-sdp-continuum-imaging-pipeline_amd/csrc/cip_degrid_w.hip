@@ -8,7 +8,5 @@
 #endif
 
 namespace cip {
-template hipError_t launch_degrid_w<CIP_DEGRID_W>(int, dim3, hipStream_t, const double*, const double*, const RowMap&,
-                                                  const uint64_t*, const int64_t*, const Chunk*, int64_t,
-                                                  const GridGeometry&, int64_t, const double*, const DegridOut&);
+template hipError_t launch_degrid_w<CIP_DEGRID_W>(const DegridLaunch&, dim3, hipStream_t);
 }  // namespace cip

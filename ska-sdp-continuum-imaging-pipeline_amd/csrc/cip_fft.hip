@@ -699,7 +699,7 @@ __global__ __launch_bounds__(NH / 16, 4) void fft_cols_eo_kernel(const double2* 
   }
 }
 
-static bool fft_len_ok(int64_t n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192 || n == 16384; }
+static bool fft_len_ok(int64_t n) { return list_has(FftLengths{}, n); }
 
 bool fast_fft_supported(int64_t nu, int64_t nv, int64_t nx, int64_t ny) {
   return fft_len_ok(nu) && fft_len_ok(nv) && nx > 0 && ny > 0 && nx <= nu && ny <= nv && nx % kColBlock == 0 &&
@@ -710,60 +710,42 @@ bool fft_cols_eo(int64_t nv, int64_t ny, bool grid_f32, int mode) {
   return CIP_FFT_EO && nv == 16384 && ny <= nv / 2 && !grid_f32 && mode == 0;
 }
 
+// the cell types the launchers below choose among
+constexpr type_tag<float2> kC64{};
+constexpr type_tag<double2> kC128{};
+
 hipError_t launch_fft_rows(double* gT, int64_t nu, int64_t nv, int64_t nx, const double* tw_u, double* H,
-                           const uint32_t* dmask, int64_t ntx, bool skip_clean, hipStream_t s, bool grid_f32,
-                           bool eo) {
+                           const uint32_t* dmask, int64_t ntx, bool skip_clean, bool grid_f32, bool eo,
+                           hipStream_t s) {
   if (!fft_len_ok(nu) || !fft_len_ok(nv) || nx > nu) return hipErrorInvalidValue;
   if (eo && (grid_f32 || nv % 2 != 0)) return hipErrorInvalidValue;
   if (dmask && (nu % kTile != 0 || nv % kTile != 0 || ntx * kTile != nu || ntx % 32 != 0))
     return hipErrorInvalidValue;
   const dim3 gd((unsigned)nv);
-  double2* g = (double2*)gT;
-  float2* gf = (float2*)gT;
   const double2* tw = (const double2*)tw_u;
-  double2* h = (double2*)H;
-  float2* hf = (float2*)H;  // complex64 planes: complex64 pass-A output
   const bool fft_f32 = fft_f32_enabled();
-#define ROWS(NN)                                                                                              \
-  case NN:                                                                                                    \
-    if (grid_f32 && dmask && fft_f32)                                                                         \
-      fft_rows_kernel<NN, true, false, float2, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(                  \
-          gf, nv, nx, tw, hf, dmask, ntx, 0, 0, skip_clean);                                                  \
-    else if (grid_f32 && fft_f32)                                                                             \
-      fft_rows_kernel<NN, false, false, float2, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(gf, nv, nx, tw,  \
-                                                                                             hf, nullptr, 0); \
-    else if (grid_f32 && dmask)                                                                               \
-      fft_rows_kernel<NN, true, false, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(gf, nv, nx, tw, hf, dmask, \
-                                                                                    ntx, 0, 0, skip_clean);   \
-    else if (grid_f32)                                                                                        \
-      fft_rows_kernel<NN, false, false, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(gf, nv, nx, tw, hf,      \
-                                                                                     nullptr, 0);             \
-    else if (dmask && eo)                                                                                     \
-      fft_rows_kernel<NN, true, false, double2, double2, double2, true><<<gd, dim3(NN / 16), 0, s>>>(         \
-          g, nv, nx, tw, h, dmask, ntx, 0, 0, skip_clean);                                                    \
-    else if (eo)                                                                                              \
-      fft_rows_kernel<NN, false, false, double2, double2, double2, true><<<gd, dim3(NN / 16), 0, s>>>(        \
-          g, nv, nx, tw, h, nullptr, 0);                                                                      \
-    else if (dmask)                                                                                           \
-      fft_rows_kernel<NN, true><<<gd, dim3(NN / 16), 0, s>>>(g, nv, nx, tw, h, dmask, ntx, 0, 0, skip_clean); \
-    else                                                                                                      \
-      fft_rows_kernel<NN, false><<<gd, dim3(NN / 16), 0, s>>>(g, nv, nx, tw, h, nullptr, 0);                  \
-    break;
-  switch (nu) {
-    ROWS(1024)
-    ROWS(2048)
-    ROWS(4096)
-    ROWS(8192)
-    ROWS(16384)
-    default: return hipErrorInvalidValue;
-  }
-#undef ROWS
-  return hipGetLastError();
+  return dispatch_int(FftLengths{}, nu, hipErrorInvalidValue, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    // planes and H of GT cells (complex64 planes: complex64 pass-A output),
+    // transformed in CT; eo_c: H in even / odd halves
+    auto rows = [&](auto gt, auto ct, auto eo_c) {
+      using GT = typename decltype(gt)::type;
+      using CT = typename decltype(ct)::type;
+      return dispatch_bool(dmask != nullptr, [&](auto masked) {
+        constexpr bool M = decltype(masked)::value;
+        fft_rows_kernel<N, M, false, GT, GT, CT, decltype(eo_c)::value><<<gd, dim3(N / 16), 0, s>>>(
+            (GT*)gT, nv, nx, tw, (GT*)H, dmask, M ? ntx : 0, 0, 0, M && skip_clean);
+        return hipGetLastError();
+      });
+    };
+    if (grid_f32) return fft_f32 ? rows(kC64, kC64, std::false_type{}) : rows(kC64, kC128, std::false_type{});
+    return eo ? rows(kC128, kC128, std::true_type{}) : rows(kC128, kC128, std::false_type{});
+  });
 }
 
 hipError_t launch_fft_rows_strip(double* gT, int64_t nu, int64_t nv, int64_t nx, const double* tw_u, int64_t y0,
-                                 int64_t y1, double* H, hipStream_t s, const uint32_t* dmask, int64_t row0,
-                                 const int64_t* row_slot, int64_t nlive) {
+                                 int64_t y1, double* H, const uint32_t* dmask, int64_t row0,
+                                 const int64_t* row_slot, int64_t nlive, hipStream_t s) {
   if (!fft_len_ok(nu) || !fft_len_ok(nv) || nx > nu || y0 < 0 || y1 > nv || y1 <= y0) return hipErrorInvalidValue;
   if (dmask && (nu % kTile != 0 || nv % kTile != 0 || (nu / kTile) % 32 != 0)) return hipErrorInvalidValue;
   const dim3 gd((unsigned)(y1 - y0));
@@ -771,92 +753,56 @@ hipError_t launch_fft_rows_strip(double* gT, int64_t nu, int64_t nv, int64_t nx,
   const double2* tw = (const double2*)tw_u;
   double2* h = (double2*)H;
   const int64_t ntx = nu / kTile;
-#define ROWS(NN)                                                                                               \
-  case NN:                                                                                                     \
-    if (dmask)                                                                                                 \
-      fft_rows_kernel<NN, true, false><<<gd, dim3(NN / 16), 0, s>>>(g, row_slot ? nlive : y1 - y0, nx, tw, h,   \
-                                                                     dmask, ntx, y0, y0, false, row0, nv,      \
-                                                                     row_slot);                                \
-    else                                                                                                       \
-      fft_rows_kernel<NN, false, true><<<gd, dim3(NN / 16), 0, s>>>(g, y1 - y0, nx, tw, h, nullptr, 0, y0, y0); \
-    break;
-  switch (nu) {
-    ROWS(1024)
-    ROWS(2048)
-    ROWS(4096)
-    ROWS(8192)
-    ROWS(16384)
-    default: return hipErrorInvalidValue;
-  }
-#undef ROWS
-  return hipGetLastError();
+  return dispatch_int(FftLengths{}, nu, hipErrorInvalidValue, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    // masked: only the dirty tiles are read and zeroed; else every cell read is
+    if (dmask)
+      fft_rows_kernel<N, true, false><<<gd, dim3(N / 16), 0, s>>>(g, row_slot ? nlive : y1 - y0, nx, tw, h, dmask, ntx,
+                                                                  y0, y0, false, row0, nv, row_slot);
+    else
+      fft_rows_kernel<N, false, true><<<gd, dim3(N / 16), 0, s>>>(g, y1 - y0, nx, tw, h, nullptr, 0, y0, y0);
+    return hipGetLastError();
+  });
+}
+
+// pass B of a strip's image rows [i0, i1) in fp64: MODE 0 / 1 as launch_fft_cols
+template <int MODE>
+static hipError_t fft_cols_strip(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v, int64_t i0,
+                                 int64_t i1, const ColEpilogue& ep, hipStream_t s) {
+  if (i0 < 0 || i1 > nx || i1 <= i0 || i0 % kColBlock != 0 || (i1 - i0) % kColBlock != 0)
+    return hipErrorInvalidValue;
+  const dim3 gd((unsigned)(i1 - i0));
+  return dispatch_int(FftLengths{}, nv, hipErrorInvalidValue, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    fft_cols_kernel<N, MODE><<<gd, dim3(N / 16), 0, s>>>((const double2*)H, nx, ny, (const double2*)tw_v, ep, i0);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_fft_cols_strip(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v, int64_t i0,
                                  int64_t i1, double* out, const double* cx, const double* cy, const double* norm,
                                  hipStream_t s) {
-  if (i0 < 0 || i1 > nx || i1 <= i0 || i0 % kColBlock != 0 || (i1 - i0) % kColBlock != 0)
-    return hipErrorInvalidValue;
-  const dim3 gd((unsigned)(i1 - i0));
-  const double2* h = (const double2*)H;
-  const double2* tw = (const double2*)tw_v;
-  const ColEpilogue ep{out, cx, cy, 0.0, 0.0, 0.0, 1, norm};
-#define COLS(NN)                                                                          \
-  case NN:                                                                                \
-    fft_cols_kernel<NN, 0><<<gd, dim3(NN / 16), 0, s>>>(h, nx, ny, tw, ep, i0);           \
-    break;
-  switch (nv) {
-    COLS(1024)
-    COLS(2048)
-    COLS(4096)
-    COLS(8192)
-    COLS(16384)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef COLS
-  return hipGetLastError();
+  return fft_cols_strip<0>(H, nv, nx, ny, tw_v, i0, i1, ColEpilogue{out, cx, cy, 0.0, 0.0, 0.0, 1, norm}, s);
 }
 
 hipError_t launch_fft_cols_strip_wplane(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v,
                                         int64_t i0, int64_t i1, double* acc, double px, double py, double w_plane,
                                         bool first, hipStream_t s) {
-  if (i0 < 0 || i1 > nx || i1 <= i0 || i0 % kColBlock != 0 || (i1 - i0) % kColBlock != 0)
-    return hipErrorInvalidValue;
-  const dim3 gd((unsigned)(i1 - i0));
-  const double2* h = (const double2*)H;
-  const double2* tw = (const double2*)tw_v;
-  const ColEpilogue ep{acc, nullptr, nullptr, px, py, w_plane, first ? 1 : 0, nullptr};
-#define COLS(NN)                                                                \
-  case NN:                                                                      \
-    fft_cols_kernel<NN, 1><<<gd, dim3(NN / 16), 0, s>>>(h, nx, ny, tw, ep, i0); \
-    break;
-  switch (nv) {
-    COLS(1024)
-    COLS(2048)
-    COLS(4096)
-    COLS(8192)
-    COLS(16384)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef COLS
-  return hipGetLastError();
+  return fft_cols_strip<1>(H, nv, nx, ny, tw_v, i0, i1,
+                           ColEpilogue{acc, nullptr, nullptr, px, py, w_plane, first ? 1 : 0, nullptr}, s);
 }
 
 hipError_t launch_fft_cols(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v, int mode,
                            double* out, const double* cx, const double* cy, double px, double py, double w_plane,
-                           int first, const double* norm, const uint32_t* rowbits, hipStream_t s, bool h_f32,
-                           bool acc_f32, bool eo) {
+                           int first, const double* norm, const uint32_t* rowbits, bool h_f32, bool acc_f32,
+                           bool eo, hipStream_t s) {
   const dim3 gd((unsigned)nx);
-  const double2* h = (const double2*)H;
-  const float2* hf = (const float2*)H;
   const double2* tw = (const double2*)tw_v;
   const ColEpilogue ep{out, cx, cy, px, py, w_plane, first, norm};
   if (eo) {
     // pass A wrote the even / odd H halves (launch_fft_rows eo)
     if (!fft_cols_eo(nv, ny, h_f32, mode)) return hipErrorInvalidValue;
-    fft_cols_eo_kernel<8192><<<gd, dim3(8192 / 16), 0, s>>>(h, nx, ny, tw, ep, rowbits);
+    fft_cols_eo_kernel<8192><<<gd, dim3(8192 / 16), 0, s>>>((const double2*)H, nx, ny, tw, ep, rowbits);
     return hipGetLastError();
   }
   const bool fft_f32 = fft_f32_enabled();
@@ -864,31 +810,23 @@ hipError_t launch_fft_cols(const double* H, int64_t nv, int64_t nx, int64_t ny, 
   // complex64 planes (with CIP_FFT_F32=0 the fp64-output kernel
   // would write doubles across twice the float buffer's bytes)
   if (acc_f32 && !(h_f32 && fft_f32 && mode == 1)) return hipErrorInvalidValue;
-#define COLS(NN)                                                                                           \
-  case NN:                                                                                                 \
-    if (h_f32 && fft_f32 && mode == 1 && acc_f32)                                                          \
-      fft_cols_kernel<NN, 1, float2, float2, float><<<gd, dim3(NN / 16), 0, s>>>(hf, nx, ny, tw, ep, 0,     \
-                                                                                 rowbits);                \
-    else if (h_f32 && fft_f32 && mode == 0)                                                                \
-      fft_cols_kernel<NN, 0, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(hf, nx, ny, tw, ep, 0, rowbits);  \
-    else if (h_f32 && fft_f32)                                                                             \
-      fft_cols_kernel<NN, 1, float2, float2><<<gd, dim3(NN / 16), 0, s>>>(hf, nx, ny, tw, ep, 0, rowbits);  \
-    else if (h_f32 && mode == 0) fft_cols_kernel<NN, 0, float2><<<gd, dim3(NN / 16), 0, s>>>(hf, nx, ny, tw, ep, 0, rowbits); \
-    else if (h_f32) fft_cols_kernel<NN, 1, float2><<<gd, dim3(NN / 16), 0, s>>>(hf, nx, ny, tw, ep, 0, rowbits);         \
-    else if (mode == 0) fft_cols_kernel<NN, 0><<<gd, dim3(NN / 16), 0, s>>>(h, nx, ny, tw, ep, 0, rowbits); \
-    else fft_cols_kernel<NN, 1><<<gd, dim3(NN / 16), 0, s>>>(h, nx, ny, tw, ep, 0, rowbits);              \
-    break;
-  switch (nv) {
-    COLS(1024)
-    COLS(2048)
-    COLS(4096)
-    COLS(8192)
-    COLS(16384)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef COLS
-  return hipGetLastError();
+  return dispatch_int(FftLengths{}, nv, hipErrorInvalidValue, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    return dispatch_bool(mode == 0, [&](auto crop) {
+      constexpr int MODE = decltype(crop)::value ? 0 : 1;
+      // H of HT cells, transformed in CT, accumulated into OT
+      auto cols = [&](auto ht, auto ct, auto ot) {
+        using HT = typename decltype(ht)::type;
+        fft_cols_kernel<N, MODE, HT, typename decltype(ct)::type, typename decltype(ot)::type>
+            <<<gd, dim3(N / 16), 0, s>>>((const HT*)H, nx, ny, tw, ep, 0, rowbits);
+        return hipGetLastError();
+      };
+      if constexpr (MODE == 1)
+        if (acc_f32) return cols(kC64, kC64, type_tag<float>{});
+      if (h_f32) return fft_f32 ? cols(kC64, kC64, type_tag<double>{}) : cols(kC64, kC128, type_tag<double>{});
+      return cols(kC128, kC128, type_tag<double>{});
+    });
+  });
 }
 
 // out[k] /= *sumw (CIP_NORMALISE on the paths without the fused epilogue)

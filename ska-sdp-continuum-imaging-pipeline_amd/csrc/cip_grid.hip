@@ -292,102 +292,60 @@ __global__ __launch_bounds__(kOrderThreads, 8) void order_kernel(const uint8_t* 
 // leave it free) and the lane scatter's support gives a full cycle (dP = (T +
 // W - 1) mod 16 odd)
 bool order_phases_ok(const RowMap& m, int support) {
-  auto bits = [](int64_t n) {
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < n) ++b;
-    return b;
-  };
   const int wide = m.delta == nullptr ? 0 : (m.pk_cbits ? 2 : 1);
   const bool spare = wide == 0 ? m.nvis < ((int64_t)1 << 31)
-                               : (wide == 1 || m.pk_cbits + m.pk_rbits + bits(m.nvis) <= 63);
+                               : (wide == 1 || m.pk_cbits + m.pk_rbits + index_bits(m.nvis) <= 63);
   const int nc = order_classes32() ? 32 : 16;
   const int dP = (kTile + support - 1) & (nc - 1);
   return spare && support >= 2 && support <= 16 && (dP & 1);
 }
 
 hipError_t launch_order(const uint8_t* vis_class, const RowMap& m, const uint64_t* runs, const int64_t* run_goff,
-                        const Chunk* windows, int64_t nwindows, void* perm, hipStream_t s, int phase_support) {
+                        const Chunk* windows, int64_t nwindows, void* perm, int phase_support, hipStream_t s) {
   if (nwindows <= 0) return hipSuccess;
   if (!vis_class) return hipErrorInvalidValue;
-#define ORDER(WI, PHV, NCV)                                                                                    \
-  order_kernel<WI, PHV, NCV><<<dim3((unsigned)nwindows), dim3(kOrderThreads), 0, s>>>(vis_class, m, runs,     \
-                                                                                      run_goff, windows, perm, dP)
   // ragged row slices: u64 entries (2: packed (index, row, channel))
   const int wide = m.delta == nullptr ? 0 : (m.pk_cbits ? 2 : 1);
   // 8-byte LDS atomics are banked like ds_write_b64 (MI355X_MICROARCH.md, LDS:
   // four 16-lane groups, bank pair = element mod 16), so the classes are the
   // footprint origin's element mod 16 (mod 32 before round 6)
-  const bool c32 = order_classes32();
-  const int nc = c32 ? 32 : 16;
+  const int nc = order_classes32() ? 32 : 16;
   const int dP = (kTile + phase_support - 1) & (nc - 1);
   const bool ph = phase_support > 0 && order_phases_ok(m, phase_support);
-  if (c32) {
-    if (wide == 2 && ph) ORDER(2, true, 32);
-    else if (wide == 2) ORDER(2, false, 32);
-    else if (wide && ph) ORDER(1, true, 32);
-    else if (wide) ORDER(1, false, 32);
-    else if (ph) ORDER(0, true, 32);
-    else ORDER(0, false, 32);
-  } else {
-    if (wide == 2 && ph) ORDER(2, true, 16);
-    else if (wide == 2) ORDER(2, false, 16);
-    else if (wide && ph) ORDER(1, true, 16);
-    else if (wide) ORDER(1, false, 16);
-    else if (ph) ORDER(0, true, 16);
-    else ORDER(0, false, 16);
-  }
-#undef ORDER
-  return hipGetLastError();
+  return dispatch_int<16, 32>(nc, hipErrorInvalidValue, [&](auto ncv) {
+    return dispatch_int<0, 1, 2>(wide, hipErrorInvalidValue, [&](auto wi) {
+      return dispatch_bool(ph, [&](auto phv) {
+        order_kernel<decltype(wi)::value, decltype(phv)::value, decltype(ncv)::value>
+            <<<dim3((unsigned)nwindows), dim3(kOrderThreads), 0, s>>>(vis_class, m, runs, run_goff, windows, perm, dP);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
-hipError_t launch_scatter(int support, int vis_dtype, int wgt_dtype, bool packed, int group, bool share_cus,
-                          bool store_private, const double* uvw,
-                          const double* fx, const void* vis, const void* wgt, const RowMap& m, const uint64_t* runs,
-                          const int64_t* run_goff, const int64_t* tile_run_off, const void* perm,
-                          const Chunk* chunks, int64_t chunk_begin, int64_t nchunks, const GridGeometry& g,
-                          int64_t plane, double fixed_scale, double* grid, hipStream_t s) {
-  if (nchunks <= 0) return hipSuccess;
-  if (packed && vis_dtype != CIP_C64 && vis_dtype != CIP_POL4I) return hipErrorInvalidValue;
-  const dim3 gd((unsigned)nchunks);
+hipError_t launch_scatter(const ScatterLaunch& a, hipStream_t s) {
+  if (a.nchunks <= 0) return hipSuccess;
+  if (a.packed && a.vis_dtype != CIP_C64 && a.vis_dtype != CIP_POL4I) return hipErrorInvalidValue;
+  const dim3 gd((unsigned)a.nchunks);
   // three blocks per CU: each needs > 160 KB / 4 of LDS (static sub-grid +
   // this pad); the 256-thread lane kernels only (plane groups run 512)
   unsigned pad = 0;
-  if (share_cus && group == 1 && support <= 16) {
-    const unsigned P = (unsigned)(kTile + support - 1);
-    const unsigned stat = P * P * (packed ? 8u : 16u) + 64u;
+  if (a.share_cus && a.group == 1 && a.support <= 16) {
+    const unsigned P = (unsigned)(kTile + a.support - 1);
+    const unsigned stat = P * P * (a.packed ? 8u : 16u) + 64u;
     // 3 blocks per CU: the optimum of 2 / 3 / 4 (profiles/r03_ab_scatter_share.txt, r05z_ab_share_blocks.txt)
     const unsigned nb = 3u;
     const unsigned need = 160u * 1024u / (nb + 1u) + 256u;
     pad = stat < need ? need - stat : 0u;
   }
-#define CASE(WW)                                                                                             \
-  case WW:                                                                                                   \
-    return launch_scatter_w<WW>(vis_dtype, wgt_dtype, packed, group, pad, store_private ? 1 : 0, gd, s, uvw, fx,  \
-                                vis, wgt, m, runs, \
-                                  run_goff, tile_run_off, perm, chunks, chunk_begin, g, plane, fixed_scale, grid);
-  switch (support) {
-    CASE(4)
-    CASE(6)
-    CASE(8)
-    CASE(10)
-    CASE(12)
-    CASE(14)
-    CASE(16)
-#define LARGE(WW)                                                                                              \
-  case WW:                                                                                                     \
-    /* wave-per-visibility scatter (cip_scatter_large.hip); fp64 class, one plane per unit */                  \
-    if (packed || group != 1) return hipErrorInvalidValue;                                                     \
-    return launch_scatter_large_w<WW>(vis_dtype, wgt_dtype, gd, s, uvw, fx, vis, wgt, m, runs, run_goff, perm, \
-                                      chunks, chunk_begin, g, plane, fixed_scale, grid);
-    LARGE(24)
-    LARGE(32)
-    LARGE(48)
-    LARGE(64)
-#undef LARGE
-    default:
-      return hipErrorInvalidValue;
+  if (list_has(LargeSupports{}, a.support)) {
+    // wave-per-visibility scatter (cip_scatter_large.hip); fp64 class, one plane per unit
+    if (a.packed || a.group != 1) return hipErrorInvalidValue;
+    return dispatch_int(LargeSupports{}, a.support, hipErrorInvalidValue,
+                        [&](auto w) { return launch_scatter_large_w<decltype(w)::value>(a, gd, s); });
   }
-#undef CASE
+  return dispatch_int(LaneSupports{}, a.support, hipErrorInvalidValue,
+                      [&](auto w) { return launch_scatter_w<decltype(w)::value>(a, gd, pad, s); });
 }
 
 // ---------------------------------------------------- post-FFT kernels ----
@@ -476,8 +434,8 @@ __global__ void wfinal_correct_kernel(const AT* __restrict__ acc, double* __rest
 
 hipError_t launch_wfinal_correct(double* acc, int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y,
                                  const double* cx, const double* cy, const double* fw_table, int64_t fw_n,
-                                 double fw_dnu, double dw, hipStream_t s, int64_t i0, int64_t nrows,
-                                 const double* norm, const float* acc_f32) {
+                                 double fw_dnu, double dw, int64_t i0, int64_t nrows, const double* norm,
+                                 const float* acc_f32, hipStream_t s) {
   if (nrows < 0) nrows = npix_x - i0;
   if (nrows <= 0) return hipSuccess;
   const dim3 gd((unsigned)((npix_y + 255) / 256), (unsigned)nrows);

@@ -31,10 +31,10 @@ bool order_classes32();  // CIP_ORDER_CLASSES (cip_grid.hip)
 int64_t scan_tmp_elems(int64_t n);
 // run_goff[k] = sum of the lengths of runs [0, k), k in [0, nruns] (fused
 // run-length + exclusive scan)
-// run lengths from the run records, or (run_keys, RowMap::pk_runs) from the
-// sorted keys' bits 26-31
-hipError_t scan_run_offsets(const uint64_t* runs, int64_t nruns, int64_t* run_goff, int64_t* tmp, hipStream_t s,
-                            const uint32_t* run_keys = nullptr);
+// run lengths from the run records, or (run_keys not NULL, RowMap::pk_runs)
+// from the sorted keys' bits 26-31
+hipError_t scan_run_offsets(const uint64_t* runs, int64_t nruns, int64_t* run_goff, int64_t* tmp,
+                            const uint32_t* run_keys, hipStream_t s);
 hipError_t exclusive_scan_i64(int64_t* data, int64_t n, int64_t* tmp, hipStream_t s);
 
 // ---- gridder planner (cip_plan.hip) ----------------------------------------
@@ -79,15 +79,15 @@ hipError_t launch_radix_group_hist(const int64_t* hist0, int64_t nsub, int G, in
 hipError_t launch_radix_scatter(const uint32_t* keys, const uint64_t* vals, int64_t n, const int64_t* blk_cnt,
                                 int64_t nsub, int G, int shift, const int64_t* hist, uint32_t* keys_out,
                                 uint64_t* vals_out, hipStream_t s);
+// kmask: the key bits that hold the tile (kRunKeyMask under RowMap::pk_runs, else all)
 hipError_t launch_tile_offsets(const uint32_t* keys, int64_t nruns, int64_t ntiles, int64_t* tile_run_off,
-                               hipStream_t s, uint32_t kmask = 0xffffffffu);
+                               uint32_t kmask, hipStream_t s);
 // per grid plane (nplanes x ntx x nty bytes); bits (optional, ntx % 32 ==
 // 0): the masks bit-packed, ntx / 32 words per tile row, ntx nty / 32 per plane
 hipError_t launch_dirty_mask(const int64_t* tile_vis, int64_t ntx, int64_t nty, int64_t ntw, int support,
                              int64_t nplanes, uint8_t* mask, uint32_t* bits, hipStream_t s);
 hipError_t launch_tile_vis(const int64_t* run_goff, const int64_t* tile_run_off, int64_t ntiles,
                            int64_t* tile_vis_off, int64_t* tile_vis, hipStream_t s);
-hipError_t launch_run_lengths(const uint64_t* runs, int64_t nruns, int64_t* out, hipStream_t s);
 // full_first: full chunks of every tile before the partial ones (chunk_off
 // then has 2 ntiles + 1 entries), else per tile in tile order (ntiles + 1)
 hipError_t launch_chunk_counts(const int64_t* tile_vis, int64_t ntiles, int64_t chunk_vis, int full_first,
@@ -109,40 +109,52 @@ hipError_t launch_gather_i64(const int64_t* src, int64_t stride, int64_t count, 
 // out2 = {sum, max} of the place pass's 2 * nblocks partials
 hipError_t launch_add_scalar(const double* src, double* dst, hipStream_t s);
 hipError_t launch_prep_final(const double* partial, int nblocks, double* out2, hipStream_t s);
-// packed: single-precision class (re/im packed in one 64-bit integer), complex64
-// only. perm: bank-class ordered stream from launch_order, or NULL (visibilities
+// The plan as the scatter and the degridder read it: the visibilities and the
+// planner's buffers that index them (the degridder reads neither vis, wgt,
+// tile_run_off nor perm).
+// perm: bank-class ordered stream from launch_order, or NULL (visibilities
 // located through the tile's row slices in tile order).
-// one kernel support W (instantiated in cip_scatter_w.hip for W = 4, 6, ..., 16)
-template <int W>
-hipError_t launch_scatter_w(int vis_dtype, int wgt_dtype, bool pack, int group, unsigned lds_extra,
-                            int store_private, dim3 gd, hipStream_t s,
-                            const double* uvw,
-                            const double* fx, const void* vis, const void* wgt, const RowMap& m,
-                            const uint64_t* runs, const int64_t* run_goff, const int64_t* tile_run_off,
-                            const void* perm, const Chunk* chunks, int64_t cb, const GridGeometry& g,
-                            int64_t plane, double fs, double* grid);
-// the large supports W = 24, 32, 48, 64 (cip_scatter_large.hip, wave per
-// visibility; one translation unit per W)
-template <int W>
-hipError_t launch_scatter_large_w(int vis_dtype, int wgt_dtype, dim3 gd, hipStream_t s, const double* uvw,
-                                  const double* fx, const void* vis, const void* wgt, const RowMap& m,
-                                  const uint64_t* runs, const int64_t* run_goff, const void* perm,
-                                  const Chunk* chunks, int64_t cb, const GridGeometry& g, int64_t plane, double fs,
-                                  double* grid);
-// group: w planes per work unit (w-stacking plane groups, 1 or 2; grid = the
-// group's planes, 2 nu nv doubles apart)
+struct PlanView {
+  const double *uvw = nullptr, *fx = nullptr;
+  const void *vis = nullptr, *wgt = nullptr;
+  RowMap m;
+  const uint64_t* runs = nullptr;
+  const int64_t *run_goff = nullptr, *tile_run_off = nullptr;
+  const void* perm = nullptr;
+  const Chunk* chunks = nullptr;
+};
+// One scatter launch: work units [chunk_begin, chunk_begin + nchunks) of the
+// plan onto planes plane .. plane + group - 1 of grid.
+// packed: single-precision class (re/im packed in one 64-bit integer), complex64
+// and raw linear-feed input only.
+// group: w planes per work unit (w-stacking plane groups; grid = the group's
+// planes, 2 nu nv doubles apart)
 // share_cus: cap the scatter at three 256-thread blocks per CU (extra dynamic
 // LDS) so kernels of another stream - the next pipelined call's planner - run
 // beside it
 // store_private: the grid planes are zero (a cip_ms2dirty plane, not an
 // accumulating one), so a tile's only work unit stores its private cells
-hipError_t launch_scatter(int support, int vis_dtype, int wgt_dtype, bool packed, int group, bool share_cus,
-                          bool store_private,
-                          const double* uvw,
-                          const double* fx, const void* vis, const void* wgt, const RowMap& m, const uint64_t* runs,
-                          const int64_t* run_goff, const int64_t* tile_run_off, const void* perm,
-                          const Chunk* chunks, int64_t chunk_begin, int64_t nchunks, const GridGeometry& g,
-                          int64_t plane, double fixed_scale, double* grid, hipStream_t s);
+struct ScatterLaunch {
+  PlanView plan;
+  int64_t chunk_begin = 0, nchunks = 0;
+  GridGeometry g;
+  int64_t plane = 0;
+  double fixed_scale = 1.0;
+  double* grid = nullptr;
+  int support = 0, vis_dtype = CIP_C64, wgt_dtype = CIP_NONE;
+  bool packed = false;
+  int group = 1;
+  bool share_cus = false, store_private = false;
+};
+// one kernel support W (instantiated in cip_scatter_w.hip for W = 4, 6, ..., 16);
+// lds_extra: share_cus's dynamic LDS pad
+template <int W>
+hipError_t launch_scatter_w(const ScatterLaunch& a, dim3 gd, unsigned lds_extra, hipStream_t s);
+// the large supports W = 24, 32, 48, 64 (cip_scatter_large.hip, wave per
+// visibility; one translation unit per W)
+template <int W>
+hipError_t launch_scatter_large_w(const ScatterLaunch& a, dim3 gd, hipStream_t s);
+hipError_t launch_scatter(const ScatterLaunch& a, hipStream_t s);
 // perm (nvis 32-bit records, nvis < 2^32): the tile-order visibilities as
 // row * nchan + channel, bank-class sorted within each window (the tiles split
 // into <= kOrderWindow pieces by chunk_emit with cv = kOrderWindow)
@@ -152,20 +164,21 @@ hipError_t launch_scatter(int support, int vis_dtype, int wgt_dtype, bool packed
 // 0: no phases
 // (phases only where order_phases_ok; the scatter then needs RowMap::row_phase)
 hipError_t launch_order(const uint8_t* vis_class, const RowMap& m, const uint64_t* runs, const int64_t* run_goff,
-                        const Chunk* windows, int64_t nwindows, void* perm, hipStream_t s, int phase_support = 0);
+                        const Chunk* windows, int64_t nwindows, void* perm, int phase_support, hipStream_t s);
 bool order_phases_ok(const RowMap& m, int support);
 hipError_t launch_crop_correct_2d(const double* grid, const GridGeometry& g, int64_t npix_x, int64_t npix_y,
                                   const double* cx, const double* cy, double* dirty, hipStream_t s);
 hipError_t launch_wplane_accumulate(const double* grid, const GridGeometry& g, int64_t npix_x, int64_t npix_y,
                                     double pixsize_x, double pixsize_y, double w_plane, int first,
                                     double* acc, hipStream_t s);
-// image rows [i0, i0 + nrows) held as acc rows 0.. (nrows < 0: to npix_x);
-// norm (may be NULL): also / *norm; acc_f32 (may be NULL): the planes were
-// accumulated in this float buffer (the packed class) - corrected into acc
+// image rows [i0, i0 + nrows) held as acc rows 0.. (nrows < 0: to npix_x; the
+// whole image is i0 = 0, nrows = -1); norm (may be NULL): also / *norm;
+// acc_f32 (may be NULL): the planes were accumulated in this float buffer (the
+// packed class) - corrected into acc
 hipError_t launch_wfinal_correct(double* acc, int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y,
                                  const double* cx, const double* cy, const double* fw_table, int64_t fw_n,
-                                 double fw_dnu, double dw, hipStream_t s, int64_t i0 = 0, int64_t nrows = -1,
-                                 const double* norm = nullptr, const float* acc_f32 = nullptr);
+                                 double fw_dnu, double dw, int64_t i0, int64_t nrows, const double* norm,
+                                 const float* acc_f32, hipStream_t s);
 
 // ---- degridding (cip_degrid.h, cip_degrid.hip) -----------------------------
 // Where a degrid launch puts its values.
@@ -183,18 +196,22 @@ struct DegridOut {
   int subtract;
   double2* acc;
 };
+// One degrid launch: work units [chunk_begin, chunk_begin + nchunks) of the
+// plan against the forward-transformed planes plane .. plane + group - 1 (nu
+// x nv complex128 each, g[x][y]); reads neither perm nor the row phases
+struct DegridLaunch {
+  PlanView plan;
+  int64_t chunk_begin = 0, nchunks = 0;
+  GridGeometry g;
+  int64_t plane = 0;
+  const double* planes = nullptr;
+  int support = 0, group = 1;
+  DegridOut out;
+};
 // one kernel support W (instantiated in cip_degrid_w.hip for W = 4, 6, ..., 16)
 template <int W>
-hipError_t launch_degrid_w(int group, dim3 gd, hipStream_t s, const double* uvw, const double* fx, const RowMap& m,
-                           const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t cb,
-                           const GridGeometry& g, int64_t plane, const double* planes, const DegridOut& o);
-// work units [chunk_begin, chunk_begin + nchunks) of the plan against the
-// forward-transformed planes plane .. plane + group - 1 (nu x nv complex128
-// each, g[x][y]); reads neither perm nor the row phases
-hipError_t launch_degrid(int support, int group, const double* uvw, const double* fx, const RowMap& m,
-                         const uint64_t* runs, const int64_t* run_goff, const Chunk* chunks, int64_t chunk_begin,
-                         int64_t nchunks, const GridGeometry& g, int64_t plane, const double* planes,
-                         const DegridOut& o, hipStream_t s);
+hipError_t launch_degrid_w(const DegridLaunch& a, dim3 gd, hipStream_t s);
+hipError_t launch_degrid(const DegridLaunch& a, hipStream_t s);
 // w-stacking: vis_io = / -= wgt * acc over nvis visibilities (acc may alias a
 // complex128 vis_io when not subtracting)
 hipError_t launch_degrid_finish(const DegridOut& o, int64_t nvis, hipStream_t s);
@@ -255,12 +272,12 @@ bool fast_fft_supported(int64_t nu, int64_t nv, int64_t nx, int64_t ny);
 // grid_f32: the planes hold complex64 cells (the packed class, GridGeometry::grid_f32)
 // and H complex64 values (pass A's output; launch_fft_cols with h_f32)
 hipError_t launch_fft_rows(double* gT, int64_t nu, int64_t nv, int64_t nx, const double* tw_u, double* H,
-                           const uint32_t* dmask, int64_t ntx, bool skip_clean, hipStream_t s,
-                           bool grid_f32 = false, bool eo = false);
+                           const uint32_t* dmask, int64_t ntx, bool skip_clean, bool grid_f32, bool eo,
+                           hipStream_t s);
 hipError_t launch_fft_cols(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v, int mode,
                            double* out, const double* cx, const double* cy, double px, double py, double w_plane,
-                           int first, const double* norm, const uint32_t* rowbits, hipStream_t s,
-                           bool h_f32 = false, bool acc_f32 = false, bool eo = false);
+                           int first, const double* norm, const uint32_t* rowbits, bool h_f32, bool acc_f32,
+                           bool eo, hipStream_t s);
 // pass B of a 2-D crop by even / odd column halves (fp64, nv = 16384, ny <=
 // nv / 2): pass A and pass B of one plane both take eo = fft_cols_eo(...)
 bool fft_cols_eo(int64_t nv, int64_t ny, bool grid_f32, int mode);
@@ -279,8 +296,8 @@ bool fft_f32_enabled();
 // H row row_slot[y - y0] of an H with nlive rows per block, rows with
 // row_slot < 0 (no dirty tile in their tile row) are skipped
 hipError_t launch_fft_rows_strip(double* gT, int64_t nu, int64_t nv, int64_t nx, const double* tw_u, int64_t y0,
-                                 int64_t y1, double* H, hipStream_t s, const uint32_t* dmask = nullptr,
-                                 int64_t row0 = 0, const int64_t* row_slot = nullptr, int64_t nlive = 0);
+                                 int64_t y1, double* H, const uint32_t* dmask, int64_t row0,
+                                 const int64_t* row_slot, int64_t nlive, hipStream_t s);
 hipError_t launch_fft_cols_strip(const double* H, int64_t nv, int64_t nx, int64_t ny, const double* tw_v, int64_t i0,
                                  int64_t i1, double* out, const double* cx, const double* cy, const double* norm,
                                  hipStream_t s);

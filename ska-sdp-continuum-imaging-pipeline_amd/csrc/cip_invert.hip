@@ -44,12 +44,18 @@ static int scatter_plane(const Prepared& pp, const PlanRequest& rq, int64_t q, c
   const int64_t cb = pp.plan.plane_chunk_off[k], ce = pp.plan.plane_chunk_off[k + 1];
   const int wgt_dtype = rq.wgt == nullptr ? CIP_NONE : rq.wgt_dtype;
   hipEvent_t a = g_prof.mark(s);
-  RowMap ms = pp.m;
-  ms.row_phase = pp.plan.phases ? 1 : 0;
-  CIP_HIP_CHECK(launch_scatter(g.support, rq.vis_dtype, wgt_dtype, pp.packed, G, mode.share_cus,
-                               !mode.accumulate && flush_store_enabled(g), rq.uvw, pp.fx, rq.vis, rq.wgt, ms,
-                               pp.plan.runs, pp.plan.run_goff, pp.plan.tile_run_off, pp.plan.perm, pp.plan.chunks, cb,
-                               ce - cb, g, p0, pp.fixed_scale, grid, s));
+  ScatterLaunch sc;
+  sc.plan.uvw = rq.uvw, sc.plan.fx = pp.fx, sc.plan.vis = rq.vis, sc.plan.wgt = rq.wgt;
+  sc.plan.m = pp.m;
+  sc.plan.m.row_phase = pp.plan.phases ? 1 : 0;
+  sc.plan.runs = pp.plan.runs, sc.plan.run_goff = pp.plan.run_goff, sc.plan.tile_run_off = pp.plan.tile_run_off;
+  sc.plan.perm = pp.plan.perm, sc.plan.chunks = pp.plan.chunks;
+  sc.chunk_begin = cb, sc.nchunks = ce - cb;
+  sc.g = g, sc.plane = p0, sc.fixed_scale = pp.fixed_scale, sc.grid = grid;
+  sc.support = g.support, sc.vis_dtype = rq.vis_dtype, sc.wgt_dtype = wgt_dtype;
+  sc.packed = pp.packed, sc.group = G, sc.share_cus = mode.share_cus;
+  sc.store_private = !mode.accumulate && flush_store_enabled(g);
+  CIP_HIP_CHECK(launch_scatter(sc, s));
   g_prof.span(2, a, g_prof.mark(s));
   if (ce > cb) g_prof.counts[4] += 1;
   return CIP_OK;
@@ -100,8 +106,8 @@ static int plane_to_dirty(const DirtyStage& st, const GridGeometry& g, int64_t p
   const bool eo = st.fast && fft_cols_eo(g.nv, st.npix_y, g.grid_f32 != 0, g.do_wstacking ? 1 : 0);
   if (st.fast) {
     if (!fft_rowskip()) rowbits = nullptr;
-    CIP_HIP_CHECK(launch_fft_rows(grid, g.nu, g.nv, st.npix_x, st.tw_u, st.fft_h, dmask, g.ntx, rowbits != nullptr, s,
-                                  g.grid_f32 != 0, eo));
+    CIP_HIP_CHECK(launch_fft_rows(grid, g.nu, g.nv, st.npix_x, st.tw_u, st.fft_h, dmask, g.ntx, rowbits != nullptr,
+                                  g.grid_f32 != 0, eo, s));
   } else if (hipfftExecZ2Z(st.plan, (hipfftDoubleComplex*)grid, (hipfftDoubleComplex*)grid, HIPFFT_BACKWARD) !=
              HIPFFT_SUCCESS) {
     return set_error(CIP_EHIP, "hipfftExecZ2Z failed");
@@ -111,7 +117,7 @@ static int plane_to_dirty(const DirtyStage& st, const GridGeometry& g, int64_t p
   if (st.fast)
     CIP_HIP_CHECK(launch_fft_cols(st.fft_h, g.nv, st.npix_x, st.npix_y, st.tw_v, g.do_wstacking ? 1 : 0, dirty_out,
                                   st.cx, st.cy, st.px, st.py, w_plane, first, g.do_wstacking ? nullptr : norm,
-                                  dmask ? rowbits : nullptr, s, g.grid_f32 != 0, acc_f32, eo));
+                                  dmask ? rowbits : nullptr, g.grid_f32 != 0, acc_f32, eo, s));
   hipEvent_t f1 = g_prof.mark(s);
   g_prof.span(3, f0, f1);
   if (st.fast) {
@@ -134,7 +140,7 @@ static int finish_dirty(Workspace* ws, const DirtyStage& st, const cip_gridder_p
   double dnu = 0.0;
   if (const int rc = w_correction_table(ws, prm, g, s, &fwd, &fw_n, &dnu); rc != CIP_OK) return rc;
   CIP_HIP_CHECK(launch_wfinal_correct(dirty_out, st.npix_x, st.npix_y, st.px, st.py, st.cx, st.cy, fwd, fw_n, dnu,
-                                      g.dw, s, 0, -1, nullptr, acc_f32));
+                                      g.dw, 0, -1, nullptr, acc_f32, s));
   return CIP_OK;
 }
 

@@ -115,31 +115,33 @@ int64_t scan_tmp_elems(int64_t n) {
   return total + 1;
 }
 
-static hipError_t scan_impl(int64_t* data, int64_t n, int64_t* tmp, const uint64_t* runs, hipStream_t s,
-                            const uint32_t* run_keys = nullptr) {
+// Where the scanned values come from: scan_local_kernel's RUNS and its source
+// (0: data itself, src unused)
+struct ScanLengths {
+  int kind;
+  const void* src;
+};
+static hipError_t scan_impl(int64_t* data, int64_t n, int64_t* tmp, ScanLengths from, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
-  if (run_keys)
-    scan_local_kernel<2><<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp, run_keys);
-  else if (runs)
-    scan_local_kernel<1><<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp, runs);
-  else
-    scan_local_kernel<0><<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp, nullptr);
-  hipError_t e = hipGetLastError();
+  hipError_t e = dispatch_int<0, 1, 2>(from.kind, hipErrorInvalidValue, [&](auto kind) {
+    scan_local_kernel<decltype(kind)::value><<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp, from.src);
+    return hipGetLastError();
+  });
   if (e != hipSuccess || nb == 1) return e;
-  e = scan_impl(tmp, nb, tmp + nb, nullptr, s);
+  e = scan_impl(tmp, nb, tmp + nb, ScanLengths{0, nullptr}, s);
   if (e != hipSuccess) return e;
   scan_add_kernel<<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp);
   return hipGetLastError();
 }
 
 hipError_t exclusive_scan_i64(int64_t* data, int64_t n, int64_t* tmp, hipStream_t s) {
-  return scan_impl(data, n, tmp, nullptr, s);
+  return scan_impl(data, n, tmp, ScanLengths{0, nullptr}, s);
 }
 
-hipError_t scan_run_offsets(const uint64_t* runs, int64_t nruns, int64_t* run_goff, int64_t* tmp, hipStream_t s,
-                            const uint32_t* run_keys) {
-  return scan_impl(run_goff, nruns + 1, tmp, runs, s, run_keys);
+hipError_t scan_run_offsets(const uint64_t* runs, int64_t nruns, int64_t* run_goff, int64_t* tmp,
+                            const uint32_t* run_keys, hipStream_t s) {
+  return scan_impl(run_goff, nruns + 1, tmp, run_keys ? ScanLengths{2, run_keys} : ScanLengths{1, runs}, s);
 }
 
 // ------------------------------------------------------------ helpers ----
@@ -631,23 +633,13 @@ int plan_place_blocks(int64_t nvis) { return (int)plan_blocks(nvis); }
 hipError_t launch_prep_reduce(const RowMap& m, const void* vis, int vis_dtype, const void* wgt, int wgt_dtype,
                               const GridGeometry& g, unsigned* err_flag, double* partial, hipStream_t s) {
   const dim3 gd(plan_blocks(m.nvis));
-#define REDUCE(VT, WKV)                                                                                      \
-  plan_place_kernel<VT, WKV, false><<<gd, dim3(256), 0, s>>>(nullptr, nullptr, m, (const VT*)vis, wgt, g,    \
-                                                            err_flag, nullptr, nullptr, nullptr, nullptr,   \
-                                                            partial, nullptr)
-  if (vis_dtype == CIP_POL4I) {
-    REDUCE(Pol4, WK_POL4I);
-  } else if (vis_dtype == CIP_C64) {
-    if (wgt_dtype == CIP_F32) REDUCE(float2, WK_F32);
-    else if (wgt_dtype == CIP_F64) REDUCE(float2, WK_F64);
-    else REDUCE(float2, WK_NONE);
-  } else {
-    if (wgt_dtype == CIP_F32) REDUCE(double2, WK_F32);
-    else if (wgt_dtype == CIP_F64) REDUCE(double2, WK_F64);
-    else REDUCE(double2, WK_NONE);
-  }
-#undef REDUCE
-  return hipGetLastError();
+  return dispatch_vis_wgt(vis_dtype, wgt_dtype, [&](auto vt, auto wk) {
+    using VisT = typename decltype(vt)::type;
+    constexpr int WK = decltype(wk)::value;
+    plan_place_kernel<VisT, WK, false><<<gd, dim3(256), 0, s>>>(nullptr, nullptr, m, (const VisT*)vis, wgt, g, err_flag,
+                                                                nullptr, nullptr, nullptr, nullptr, partial, nullptr);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_plan_place(const double* uvw, const double* fx, const RowMap& m,
@@ -657,38 +649,15 @@ hipError_t launch_plan_place(const double* uvw, const double* fx, const RowMap& 
   const dim3 gd(plan_blocks(m.nvis));
   const bool rows64 = place_rows64() && m.nchan > 0 && m.nvis / m.nchan < ((int64_t)1 << 31) && m.nvis < ((int64_t)1 << 37);
   const int rm = m.delta != nullptr ? 2 : (m.nchan % 64 == 0 ? (rows64 ? (g.do_wstacking ? 4 : 3) : 1) : 0);
-#define PLACE_RM(VT, WKV, RMV)                                                                                      \
-  plan_place_kernel<VT, WKV, true, RMV><<<gd, dim3(256), 0, s>>>(uvw, fx, m, (const VT*)vis, wgt, g, err_flag,     \
-                                                                 vis_class, blk_cnt, park_key, park_run, partial,   \
-                                                                 hist0)
-#define PLACE(VT, WKV)            \
-  do {                            \
-    if (rm == 4) {                \
-      PLACE_RM(VT, WKV, 4);       \
-    } else if (rm == 3) {         \
-      PLACE_RM(VT, WKV, 3);       \
-    } else if (rm == 2) {         \
-      PLACE_RM(VT, WKV, 2);       \
-    } else if (rm == 1) {         \
-      PLACE_RM(VT, WKV, 1);       \
-    } else {                      \
-      PLACE_RM(VT, WKV, 0);       \
-    }                             \
-  } while (0)
-  if (vis_dtype == CIP_POL4I) {
-    PLACE(Pol4, WK_POL4I);
-  } else if (vis_dtype == CIP_C64) {
-    if (wgt_dtype == CIP_F32) PLACE(float2, WK_F32);
-    else if (wgt_dtype == CIP_F64) PLACE(float2, WK_F64);
-    else PLACE(float2, WK_NONE);
-  } else {
-    if (wgt_dtype == CIP_F32) PLACE(double2, WK_F32);
-    else if (wgt_dtype == CIP_F64) PLACE(double2, WK_F64);
-    else PLACE(double2, WK_NONE);
-  }
-#undef PLACE
-#undef PLACE_RM
-  return hipGetLastError();
+  return dispatch_vis_wgt(vis_dtype, wgt_dtype, [&](auto vt, auto wk) {
+    using VisT = typename decltype(vt)::type;
+    constexpr int WK = decltype(wk)::value;
+    return dispatch_int<0, 1, 2, 3, 4>(rm, hipErrorInvalidValue, [&](auto rmv) {
+      plan_place_kernel<VisT, WK, true, decltype(rmv)::value><<<gd, dim3(256), 0, s>>>(
+          uvw, fx, m, (const VisT*)vis, wgt, g, err_flag, vis_class, blk_cnt, park_key, park_run, partial, hist0);
+      return hipGetLastError();
+    });
+  });
 }
 
 // ------------------------------------------------------- ragged rows ----
@@ -923,24 +892,9 @@ hipError_t launch_radix_scatter(const uint32_t* keys, const uint64_t* vals, int6
 }
 
 hipError_t launch_tile_offsets(const uint32_t* keys, int64_t nruns, int64_t ntiles, int64_t* tile_run_off,
-                               hipStream_t s, uint32_t kmask) {
+                               uint32_t kmask, hipStream_t s) {
   tile_offsets_kernel<<<dim3((unsigned)((ntiles + 256) / 256)), dim3(256), 0, s>>>(keys, nruns, ntiles, tile_run_off,
                                                                                  kmask);
-  return hipGetLastError();
-}
-
-__global__ void run_lengths_kernel(const uint64_t* runs, int64_t nruns, int64_t* out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nruns) {
-    const uint64_t rec = runs[i];
-    out[i] = (int64_t)(rec & 0xffff) - (int64_t)((rec >> 16) & 0xffff);
-  } else if (i == nruns) {
-    out[i] = 0;
-  }
-}
-
-hipError_t launch_run_lengths(const uint64_t* runs, int64_t nruns, int64_t* out, hipStream_t s) {
-  run_lengths_kernel<<<dim3((unsigned)((nruns + 256) / 256)), dim3(256), 0, s>>>(runs, nruns, out);
   return hipGetLastError();
 }
 

@@ -117,11 +117,11 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
     std::swap(rin, rout);
   }
   uint64_t* runs = rin;
-  CIP_HIP_CHECK(launch_tile_offsets(kin, nruns, ntiles, tile_runs, s, mp.pk_runs ? kRunKeyMask : 0xffffffffu));
+  CIP_HIP_CHECK(launch_tile_offsets(kin, nruns, ntiles, tile_runs, mp.pk_runs ? kRunKeyMask : 0xffffffffu, s));
   const int64_t* tile_run_off = tile_runs;
   CIP_ALLOC(run_goff, int64_t, "run_goff", nruns + 1)
   CIP_ALLOC(scan_tmp2, int64_t, "scan_tmp2", scan_tmp_elems(nruns + 1))
-  CIP_HIP_CHECK(scan_run_offsets(runs, nruns, run_goff, scan_tmp2, s, mp.pk_runs ? kin : nullptr));
+  CIP_HIP_CHECK(scan_run_offsets(runs, nruns, run_goff, scan_tmp2, mp.pk_runs ? kin : nullptr, s));
   CIP_HIP_CHECK(launch_tile_vis(run_goff, tile_run_off, ntiles, tile_vis_off, tile_vis, s));
   if (g.ntx % 32 == 0 && grid_mask()) {
     CIP_ALLOC(dmask, uint8_t, "dirty_mask", g.ntx * g.nty * g.nplanes)
@@ -189,7 +189,7 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
                                     windows, s));
     CIP_ALLOC(perm, uint32_t, "perm", ragged ? 2 * nvis : nvis)
     const bool ph = row_phases() && order_phases_ok(mp, g.support);
-    CIP_HIP_CHECK(launch_order(vis_class, mp, runs, run_goff, windows, nwin, perm, s, ph ? g.support : 0));
+    CIP_HIP_CHECK(launch_order(vis_class, mp, runs, run_goff, windows, nwin, perm, ph ? g.support : 0, s));
     pr->phases = ph;
     pr->perm = perm;
   }
@@ -270,12 +270,7 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
       m.seg_row = seg_row;
       m.nrow = nrow;
       // ordered-stream entries (index, row, channel) when they fit 64 bits
-      auto bits = [](int64_t n) {
-        int b = 1;
-        while (b < 62 && ((int64_t)1 << b) < n) ++b;
-        return b;
-      };
-      const int cb = bits(nchan), rb = bits(nrow), ib = bits(ragged->nvis);
+      const int cb = index_bits(nchan), rb = index_bits(nrow), ib = index_bits(ragged->nvis);
       if (cb + rb + ib <= 64 && ragged_pack()) {
         m.pk_cbits = cb;
         m.pk_rbits = rb;

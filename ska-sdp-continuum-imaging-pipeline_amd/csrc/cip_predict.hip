@@ -107,8 +107,13 @@ static int dirty2ms_impl(const double* uvw, int64_t nrow, const double* freq, in
     }
     hipEvent_t c = g_prof.mark(s);
     g_prof.span(3, b, c);
-    CIP_HIP_CHECK(launch_degrid(g.support, G, uvw, pp.fx, pp.m, pp.plan.runs, pp.plan.run_goff, pp.plan.chunks, cb,
-                                ce - cb, g, p0, planes, o, s));
+    DegridLaunch dg;
+    dg.plan.uvw = uvw, dg.plan.fx = pp.fx, dg.plan.m = pp.m;
+    dg.plan.runs = pp.plan.runs, dg.plan.run_goff = pp.plan.run_goff, dg.plan.chunks = pp.plan.chunks;
+    dg.chunk_begin = cb, dg.nchunks = ce - cb;
+    dg.g = g, dg.plane = p0, dg.planes = planes;
+    dg.support = g.support, dg.group = G, dg.out = o;
+    CIP_HIP_CHECK(launch_degrid(dg, s));
     g_prof.span(2, c, g_prof.mark(s));
     g_prof.counts[4] += 1;
   }

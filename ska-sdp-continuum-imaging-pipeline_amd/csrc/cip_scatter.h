@@ -579,119 +579,57 @@ __global__ __launch_bounds__(scatter_threads<G>(), CIP_SCATTER_WAVES) void scatt
   flush_subgrid<W, PACK, G, NT>(sub, g, plane, X0, Y0, ch, store_private, inv_scale, grid);
 }
 
+// Plane groups G with a kernel instance: 1 .. 3 in both classes; the packed
+// class's 8-byte cells also fit 4 / 5 sub-grids in 64 KB of static LDS and
+// 6 / 7 at two blocks per CU in 160 KB, while the support allows.
+constexpr bool scatter_group_fits(int W, bool pack, int G) {
+  const int P2 = (kTile + W - 1) * (kTile + W - 1);
+  if (G <= 3) return G >= 1;
+  return pack && G <= 7 && G * P2 * 8 + 4200 <= (G <= 5 ? 65536 : 81920);
+}
+
 template <int W, typename VisT, int WK>
-inline hipError_t scatter_dispatch_ws(bool ws, int group, bool pack, unsigned lds_extra, int store_private,
-                                      dim3 grid_dim, hipStream_t s,
-                                      const double* uvw,
-                                      const double* fx, const void* vis, const void* wgt, const RowMap& m,
-                                      const uint64_t* runs, const int64_t* run_goff, const int64_t* tile_run_off,
-                                      const void* perm, const Chunk* chunks, int64_t chunk_begin,
-                                      const GridGeometry& g, int64_t plane, double fs, double* grid) {
-#define LAUNCH(WSV, PRM, PK, GG)                                                                            \
-  scatter_kernel<W, VisT, WK, WSV, PRM, PK, GG><<<grid_dim, dim3(scatter_threads<GG>()), lds_extra, s>>>(   \
-      uvw, fx, (const VisT*)vis, wgt, m, runs, run_goff, tile_run_off, perm, chunks, chunk_begin, g, plane,    \
-      fs, 1.0 / fs, grid, store_private)
-#define LAUNCH_WS(PRM, PK)            \
-  {                                   \
-    if (ws && group == 3) {           \
-      LAUNCH(true, PRM, PK, 3);       \
-    } else if (ws && group == 2) {    \
-      LAUNCH(true, PRM, PK, 2);       \
-    } else if (ws) {                  \
-      LAUNCH(true, PRM, PK, 1);       \
-    } else {                          \
-      LAUNCH(false, PRM, PK, 1);      \
-    }                                 \
-  }
-  // the packed class's 8-byte cells fit larger plane groups (4, 5) in LDS
-#define LAUNCH_WS_PACKED(PRM)                                \
-  {                                                          \
-    bool hit = false;                                        \
-    if constexpr (kFitG7) {                                  \
-      if (ws && group == 7) {                                \
-        LAUNCH(true, PRM, true, 7);                          \
-        hit = true;                                          \
-      }                                                      \
-    }                                                        \
-    if constexpr (kFitG6) {                                  \
-      if (!hit && ws && group == 6) {                        \
-        LAUNCH(true, PRM, true, 6);                          \
-        hit = true;                                          \
-      }                                                      \
-    }                                                        \
-    if constexpr (kFitG5) {                                  \
-      if (!hit && ws && group == 5) {                        \
-        LAUNCH(true, PRM, true, 5);                          \
-        hit = true;                                          \
-      }                                                      \
-    }                                                        \
-    if constexpr (kFitG4) {                                  \
-      if (!hit && ws && group == 4) {                        \
-        LAUNCH(true, PRM, true, 4);                          \
-        hit = true;                                          \
-      }                                                      \
-    }                                                        \
-    if (!hit) LAUNCH_WS(PRM, true)                           \
-  }
+inline hipError_t scatter_dispatch_ws(const ScatterLaunch& a, dim3 grid_dim, unsigned lds_extra, hipStream_t s) {
+  const PlanView& p = a.plan;
+  const bool ws = a.g.do_wstacking != 0;
+  // perm's entries: 0 no perm, 1 dense rows (u32), 2 ragged row slices (u64)
+  const int perm_form = !p.perm ? 0 : (p.m.delta != nullptr ? 2 : 1);
+  auto launch = [&](auto pack) {
+    constexpr bool PK = decltype(pack)::value;
+    // a group without an instance, and 2-D, run one plane per work unit
+    const int group = ws && scatter_group_fits(W, PK, a.group) ? a.group : 1;
+    return dispatch_int<0, 1, 2>(perm_form, hipErrorInvalidValue, [&](auto prm) {
+      return dispatch_int<1, 2, 3, 4, 5, 6, 7>(group, hipErrorInvalidValue, [&](auto gg) {
+        constexpr int G = decltype(gg)::value;
+        auto go = [&](auto wsv) {
+          scatter_kernel<W, VisT, WK, decltype(wsv)::value, decltype(prm)::value, PK, G>
+              <<<grid_dim, dim3(scatter_threads<G>()), lds_extra, s>>>(
+                  p.uvw, p.fx, (const VisT*)p.vis, p.wgt, p.m, p.runs, p.run_goff, p.tile_run_off, p.perm, p.chunks,
+                  a.chunk_begin, a.g, a.plane, a.fixed_scale, 1.0 / a.fixed_scale, a.grid, a.store_private ? 1 : 0);
+          return hipGetLastError();
+        };
+        if constexpr (!scatter_group_fits(W, PK, G)) {
+          return hipErrorInvalidValue;  // (never chosen above)
+        } else {
+          if constexpr (G == 1)
+            if (!ws) return go(std::false_type{});
+          return go(std::true_type{});
+        }
+      });
+    });
+  };
   // the packed single-precision class exists for complex64 input only (the
   // reference's configuration; raw linear-feed columns are complex64 too)
-  // plane groups of 4 / 5 packed sub-grids while they fit 64 KB of static LDS
-  constexpr int P2 = (kTile + W - 1) * (kTile + W - 1);
-  constexpr bool kFitG5 = 5 * P2 * 8 + 4200 <= 65536;
-  // 6 / 7: two blocks per CU in 160 KB
-  constexpr bool kFitG7 = 7 * P2 * 8 + 4200 <= 81920;
-  constexpr bool kFitG6 = 6 * P2 * 8 + 4200 <= 81920;
-  constexpr bool kFitG4 = 4 * P2 * 8 + 4200 <= 65536;
-  bool done = false;
-  const bool wide = m.delta != nullptr;  // ragged row slices: u64 entries
-  if constexpr (std::is_same<VisT, float2>::value || std::is_same<VisT, Pol4>::value) {
-    if (pack) {
-      if (perm && wide) {
-        LAUNCH_WS_PACKED(2)
-      } else if (perm) {
-        LAUNCH_WS_PACKED(1)
-      } else {
-        LAUNCH_WS_PACKED(0)
-      }
-      done = true;
-    }
-  }
-  if (!done) {
-    if (perm && wide) {
-      LAUNCH_WS(2, false)
-    } else if (perm) {
-      LAUNCH_WS(1, false)
-    } else {
-      LAUNCH_WS(0, false)
-    }
-  }
-#undef LAUNCH_WS_PACKED
-#undef LAUNCH_WS
-#undef LAUNCH
-  return hipGetLastError();
+  if constexpr (std::is_same<VisT, float2>::value || std::is_same<VisT, Pol4>::value)
+    if (a.packed) return launch(std::true_type{});
+  return launch(std::false_type{});
 }
 
 template <int W>
-hipError_t launch_scatter_w(int vis_dtype, int wgt_dtype, bool pack, int group, unsigned lds_extra,
-                            int store_private, dim3 gd, hipStream_t s,
-                                     const double* uvw, const double* fx, const void* vis, const void* wgt,
-                                     const RowMap& m, const uint64_t* runs, const int64_t* run_goff,
-                                     const int64_t* tile_run_off, const void* perm, const Chunk* chunks,
-                                     int64_t cb, const GridGeometry& g, int64_t plane, double fs, double* grid) {
-  const bool ws = g.do_wstacking != 0;
-#define ARGS \
-  ws, group, pack, lds_extra, store_private, gd, s, uvw, fx, vis, wgt, m, runs, run_goff, tile_run_off, perm, \
-      chunks, cb, g, plane, fs, grid
-  if (vis_dtype == CIP_POL4I) return scatter_dispatch_ws<W, Pol4, WK_POL4I>(ARGS);
-  if (vis_dtype == CIP_C64) {
-    if (wgt_dtype == CIP_F32) return scatter_dispatch_ws<W, float2, WK_F32>(ARGS);
-    if (wgt_dtype == CIP_F64) return scatter_dispatch_ws<W, float2, WK_F64>(ARGS);
-    return scatter_dispatch_ws<W, float2, WK_NONE>(ARGS);
-  }
-  if (wgt_dtype == CIP_F32) return scatter_dispatch_ws<W, double2, WK_F32>(ARGS);
-  if (wgt_dtype == CIP_F64) return scatter_dispatch_ws<W, double2, WK_F64>(ARGS);
-  return scatter_dispatch_ws<W, double2, WK_NONE>(ARGS);
-#undef ARGS
+hipError_t launch_scatter_w(const ScatterLaunch& a, dim3 gd, unsigned lds_extra, hipStream_t s) {
+  return dispatch_vis_wgt(a.vis_dtype, a.wgt_dtype, [&](auto vt, auto wk) {
+    return scatter_dispatch_ws<W, typename decltype(vt)::type, decltype(wk)::value>(a, gd, lds_extra, s);
+  });
 }
 
 }  // namespace cip

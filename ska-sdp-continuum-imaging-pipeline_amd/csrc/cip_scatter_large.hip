@@ -191,64 +191,34 @@ __global__ __launch_bounds__(kLargeThreads) void scatter_large_kernel(
   }
 }
 
-template <int W, typename VisT, int WK, bool WSTACK, bool PERM>
-static hipError_t launch_large_one(dim3 gd, hipStream_t s, const double* uvw, const double* fx, const void* vis,
-                                   const void* wgt, const RowMap& m, const uint64_t* runs, const int64_t* run_goff,
-                                   const void* perm, const Chunk* chunks, int64_t cb, const GridGeometry& g,
-                                   int64_t plane, double fs, double* grid) {
+template <int W>
+hipError_t launch_scatter_large_w(const ScatterLaunch& a, dim3 gd, hipStream_t s) {
+  if (a.g.support != W) return hipErrorInvalidValue;
   constexpr int P = kTile + W - 1;
   constexpr size_t lds = (size_t)2 * P * P * sizeof(unsigned long long);
   static_assert(lds <= 160 * 1024, "sub-grid fits the CU's LDS");
-  auto* fn = scatter_large_kernel<W, VisT, WK, WSTACK, PERM>;
-  // more than the default 64 KiB of dynamic LDS (144 KiB at W = 64); set on
-  // every launch (the attribute belongs to the current device's function, and
-  // a host thread may drive several devices; a large-support launch runs for
-  // milliseconds)
-  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  fn<<<gd, dim3(kLargeThreads), lds, s>>>(uvw, fx, (const VisT*)vis, wgt, m, runs, run_goff, perm, chunks, cb, g,
-                                          plane, fs, 1.0 / fs, grid);
-  return hipGetLastError();
+  const PlanView& p = a.plan;
+  return dispatch_vis_wgt(a.vis_dtype, a.wgt_dtype, [&](auto vt, auto wk) {
+    using VisT = typename decltype(vt)::type;
+    return dispatch_bool(a.g.do_wstacking != 0, [&](auto wstack) {
+      return dispatch_bool(p.perm != nullptr, [&](auto perm) {
+        auto* fn = scatter_large_kernel<W, VisT, decltype(wk)::value, decltype(wstack)::value, decltype(perm)::value>;
+        // more than the default 64 KiB of dynamic LDS (144 KiB at W = 64); set on
+        // every launch (the attribute belongs to the current device's function, and
+        // a host thread may drive several devices; a large-support launch runs for
+        // milliseconds)
+        const hipError_t e =
+            hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        fn<<<gd, dim3(kLargeThreads), lds, s>>>(p.uvw, p.fx, (const VisT*)p.vis, p.wgt, p.m, p.runs, p.run_goff, p.perm,
+                                                p.chunks, a.chunk_begin, a.g, a.plane, a.fixed_scale,
+                                                1.0 / a.fixed_scale, a.grid);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
-template <int W, typename VisT, int WK>
-static hipError_t launch_large_vt(dim3 gd, hipStream_t s, const double* uvw, const double* fx, const void* vis,
-                                  const void* wgt, const RowMap& m, const uint64_t* runs, const int64_t* run_goff,
-                                  const void* perm, const Chunk* chunks, int64_t cb, const GridGeometry& g,
-                                  int64_t plane, double fs, double* grid) {
-#define ARGS gd, s, uvw, fx, vis, wgt, m, runs, run_goff, perm, chunks, cb, g, plane, fs, grid
-  if (g.do_wstacking) {
-    if (perm) return launch_large_one<W, VisT, WK, true, true>(ARGS);
-    return launch_large_one<W, VisT, WK, true, false>(ARGS);
-  }
-  if (perm) return launch_large_one<W, VisT, WK, false, true>(ARGS);
-  return launch_large_one<W, VisT, WK, false, false>(ARGS);
-#undef ARGS
-}
-
-template <int W>
-hipError_t launch_scatter_large_w(int vis_dtype, int wgt_dtype, dim3 gd, hipStream_t s, const double* uvw,
-                                  const double* fx, const void* vis, const void* wgt, const RowMap& m,
-                                  const uint64_t* runs, const int64_t* run_goff, const void* perm,
-                                  const Chunk* chunks, int64_t cb, const GridGeometry& g, int64_t plane, double fs,
-                                  double* grid) {
-  if (g.support != W) return hipErrorInvalidValue;
-#define ARGS gd, s, uvw, fx, vis, wgt, m, runs, run_goff, perm, chunks, cb, g, plane, fs, grid
-  if (vis_dtype == CIP_POL4I) return launch_large_vt<W, Pol4, WK_POL4I>(ARGS);
-  if (vis_dtype == CIP_C64) {
-    if (wgt_dtype == CIP_F32) return launch_large_vt<W, float2, WK_F32>(ARGS);
-    if (wgt_dtype == CIP_F64) return launch_large_vt<W, float2, WK_F64>(ARGS);
-    return launch_large_vt<W, float2, WK_NONE>(ARGS);
-  }
-  if (wgt_dtype == CIP_F32) return launch_large_vt<W, double2, WK_F32>(ARGS);
-  if (wgt_dtype == CIP_F64) return launch_large_vt<W, double2, WK_F64>(ARGS);
-  return launch_large_vt<W, double2, WK_NONE>(ARGS);
-#undef ARGS
-}
-
-template hipError_t launch_scatter_large_w<CIP_LARGE_W>(int, int, dim3, hipStream_t, const double*, const double*,
-                                                        const void*, const void*, const RowMap&, const uint64_t*,
-                                                        const int64_t*, const void*, const Chunk*, int64_t,
-                                                        const GridGeometry&, int64_t, double, double*);
+template hipError_t launch_scatter_large_w<CIP_LARGE_W>(const ScatterLaunch&, dim3, hipStream_t);
 
 }  // namespace cip

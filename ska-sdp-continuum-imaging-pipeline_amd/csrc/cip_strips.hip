@@ -238,20 +238,16 @@ hipError_t launch_strip_emit(const double* uvw, int64_t nrow, const double* fx, 
                              int vis_bytes, const void* wgt, int wgt_bytes, double* slice_uvw, int32_t* chan_start,
                              int32_t* chan_stop, int64_t* slice_row, void* vis_out, void* wgt_out, hipStream_t s) {
   const dim3 gd((unsigned)((nrow + 3) / 4)), bd(256);
-#define EMIT(VB, WB)                                                                                            \
-  strip_emit_kernel<VB, WB><<<gd, bd, 0, s>>>(uvw, nrow, fx, nchan, g.nv, g.scale_v, g.support / 2, y0, y1,    \
-                                              run_off, vis_off, vis, wgt, slice_uvw, chan_start, chan_stop,    \
-                                              slice_row, vis_out, wgt_out)
-  if (vis_bytes == 0) EMIT(0, 0);
-  else if (vis_bytes == 8 && wgt_bytes == 0) EMIT(8, 0);
-  else if (vis_bytes == 8 && wgt_bytes == 4) EMIT(8, 4);
-  else if (vis_bytes == 8 && wgt_bytes == 8) EMIT(8, 8);
-  else if (vis_bytes == 16 && wgt_bytes == 0) EMIT(16, 0);
-  else if (vis_bytes == 16 && wgt_bytes == 4) EMIT(16, 4);
-  else if (vis_bytes == 16 && wgt_bytes == 8) EMIT(16, 8);
-  else return hipErrorInvalidValue;
-#undef EMIT
-  return hipGetLastError();
+  auto emit = [&](auto vb, auto wb) {
+    strip_emit_kernel<decltype(vb)::value, decltype(wb)::value><<<gd, bd, 0, s>>>(
+        uvw, nrow, fx, nchan, g.nv, g.scale_v, g.support / 2, y0, y1, run_off, vis_off, vis, wgt, slice_uvw,
+        chan_start, chan_stop, slice_row, vis_out, wgt_out);
+    return hipGetLastError();
+  };
+  if (vis_bytes == 0) return emit(int_tag<0>{}, int_tag<0>{});  // no visibilities: no weights either
+  return dispatch_int<8, 16>(vis_bytes, hipErrorInvalidValue, [&](auto vb) {
+    return dispatch_int<0, 4, 8>(wgt_bytes, hipErrorInvalidValue, [&](auto wb) { return emit(vb, wb); });
+  });
 }
 
 // A strip's dirty-tile bits for its masked pass A (cip_strip_rows_masked):
@@ -387,7 +383,7 @@ static int strip_rows(void* hip_stream, double* grid, const GridGeometry& g, int
   CIP_BEGIN_CALL(hip_stream, false)
   double* tw_u = nullptr;
   if (const int rc = fft_twiddles(ws, g.nu, s, &tw_u); rc != CIP_OK) return rc;
-  CIP_HIP_CHECK(launch_fft_rows_strip(grid, g.nu, g.nv, npix_x, tw_u, y0, y1, H, s, dmask, row0, row_slot, nlive));
+  CIP_HIP_CHECK(launch_fft_rows_strip(grid, g.nu, g.nv, npix_x, tw_u, y0, y1, H, dmask, row0, row_slot, nlive, s));
   return end_call(call);
 }
 
@@ -509,8 +505,8 @@ int cip_strip_wfinal(double* acc_rows, const cip_gridder_params* params, int64_t
   double dnu = 0.0;
   if (const int rc = correction_vectors(ws, g, npix_x, npix_y, s, &cx, &cy); rc != CIP_OK) return rc;
   if (const int rc = w_correction_table(ws, *params, g, s, &fwd, &fw_n, &dnu); rc != CIP_OK) return rc;
-  CIP_HIP_CHECK(launch_wfinal_correct(acc_rows, npix_x, npix_y, pixsize_x, pixsize_y, cx, cy, fwd, fw_n, dnu, g.dw, s,
-                                      i0, i1 - i0, norm));
+  CIP_HIP_CHECK(launch_wfinal_correct(acc_rows, npix_x, npix_y, pixsize_x, pixsize_y, cx, cy, fwd, fw_n, dnu, g.dw, i0,
+                                      i1 - i0, norm, nullptr, s));
   return end_call(call);
 }
 

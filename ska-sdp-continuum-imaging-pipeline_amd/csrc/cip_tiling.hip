@@ -124,17 +124,11 @@ __global__ void stokes_kernel(const float2* __restrict__ vis4, const uint8_t* __
 hipError_t launch_stokes(int stokes, const void* vis4, const uint8_t* flags4, const float* wgt4, int64_t n,
                          void* vis_i, uint8_t* flag_i, float* wgt_i, float* eff_w, hipStream_t s) {
   const dim3 gd((unsigned)((n + 255) / 256)), bd(256);
-#define STK(K)                                                                                              \
-  stokes_kernel<K><<<gd, bd, 0, s>>>((const float2*)vis4, flags4, wgt4, n, (float2*)vis_i, flag_i, wgt_i, eff_w)
-  switch (stokes) {
-    case 0: STK(0); break;
-    case 1: STK(1); break;
-    case 2: STK(2); break;
-    case 3: STK(3); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef STK
-  return hipGetLastError();
+  return dispatch_int(StokesCodes{}, stokes, hipErrorInvalidValue, [&](auto k) {
+    stokes_kernel<decltype(k)::value><<<gd, bd, 0, s>>>((const float2*)vis4, flags4, wgt4, n, (float2*)vis_i, flag_i,
+                                                        wgt_i, eff_w);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------ facets ----
