@@ -118,7 +118,9 @@ typedef struct cip_gridder_params {
   double beta;         /* ES shape parameter (2.3 W) */
   double sigma;        /* oversampling factor (2.0) */
   int32_t do_wstacking;/* 1: w-stacking planes; 0: 2-D (w ignored) */
-  int32_t tile;        /* grid tile edge T (cells) used by the scatter */
+  int32_t tile;        /* the mask and plan unit (cells): the edge of a dirty-mask
+                        * tile; the 2-D scatter's work tile may be a multiple
+                        * of it */
   int64_t nplanes;     /* number of w planes (1 in 2-D mode) */
   double w0, dw;       /* plane p sits at w = w0 + p dw (wavelengths) */
   double nmin;         /* min over the field of n - 1 (<= 0) */

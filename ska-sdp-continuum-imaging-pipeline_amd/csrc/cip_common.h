@@ -45,12 +45,23 @@ constexpr float kMagicF = 12582912.0f;  // 1.5 * 2^23
 constexpr uint32_t kMagicFBits = 0x4B400000u;
 constexpr int kPackedGainLog2Max = 3;
 
-// Tile edge (grid cells) of the scatter work decomposition (CIP_TILE
-// overrides it in experiment builds, tools/build_variant_full.sh).
-#ifndef CIP_TILE
-#define CIP_TILE 32
-#endif
-constexpr int kTile = CIP_TILE;
+// The mask and plan unit (grid cells): the edge of a dirty-mask tile (FFT,
+// strips) and of every path's scatter tile but the 2-D lane scatter's, whose
+// work tile is a property of the plan (GridGeometry::tx_shift / ty_shift: 32
+// or 64 cells per edge, a multiple of this unit; CIP_SCATTER_TILE forces it).
+constexpr int kTileShift = 5;
+constexpr int kTile = 1 << kTileShift;
+
+// Work tiles (TX x TY cells) the 2-D lane scatter has an instance of at
+// support W (pack: the packed class's 8-byte cells): 32 x 32 always; 64 x 64
+// where two 512-thread blocks' sub-grids fit the CU's 160 KiB of LDS (fp64
+// class: W <= 8); 64 x 32 and 32 x 64 where three 256-thread blocks' do.
+constexpr bool scatter_tile_fits(int W, bool pack, int TX, int TY) {
+  if (TX == kTile && TY == kTile) return true;
+  if (W > 16) return false;
+  const int bytes = (TX + W - 1) * (TY + W - 1) * (pack ? 8 : 16) + 1024;
+  return (TX == 2 * kTile && TY == 2 * kTile ? 2 : 3) * bytes <= 160 * 1024;
+}
 
 // Visibilities per bank-class ordering window (cip_grid.hip order_kernel);
 // divides kChunkVis and kChunkVisPacked so, in 2-D mode, windows never
@@ -225,8 +236,12 @@ struct GridGeometry {
   double w0, dw;
   double inv_dw;  // 1 / dw: the w coordinate (w f / c - w0) / dw as one multiply (planner, scatter, oracle alike)
   int64_t nplanes;
-  int tile;                 // T
-  int64_t ntx, nty, ntw;    // tiles per axis (ntw = nplanes - W + 1, or 1 in 2-D)
+  int tile;                 // the mask unit (kTile)
+  // the scatter's work tile: 2^tx_shift x 2^ty_shift cells (5 or 6 each; 6 only
+  // on the 2-D lane scatter, scatter_tile_shape in cip_params.hip)
+  int tx_shift, ty_shift;
+  int64_t ntx, nty, ntw;    // work tiles per axis (ntw = nplanes - W + 1, or 1 in 2-D)
+  int64_t mtx, mty;         // mask tiles (kTile cells) per axis: the dirty masks' layout
   int transposed;           // HBM grid stored as gT[y, x] (pruned FFT), else g[x, y]
   // row window of the HBM buffer (transposed layout; uv-strip ranks, DESIGN.md
   // 7): buffer row k holds grid row (row0 + k) mod nv, k < rows. The whole
@@ -249,21 +264,21 @@ struct GridGeometry {
   uint32_t* wmask;
 };
 
-// The flush's report to GridGeometry::wmask: `bits` = the tiles of one work
-// unit's sub-grid its flush wrote, bit dx * 3 + dy for tile (X0 / T + dx,
-// Y0 / T + dy) (wrapped; dx, dy <= 2: the sub-grid spans T + W - 1 <= 95
+// The flush's report to GridGeometry::wmask: `bits` = the mask tiles of one
+// work unit's sub-grid its flush wrote, bit dx * 3 + dy for mask tile (X0 / 32
+// + dx, Y0 / 32 + dy) (wrapped; dx, dy <= 2: the sub-grid spans at most 95
 // cells), plane p. A handful of device atomics per work unit.
 __device__ __forceinline__ void wmask_report(const GridGeometry& g, int64_t p, int64_t X0, int64_t Y0,
                                              unsigned bits) {
-  const int64_t tx0 = X0 / kTile, ty0 = Y0 / kTile;
-  const int64_t wpr = g.ntx / 32;
-  uint32_t* m = g.wmask + p * g.nty * wpr;
+  const int64_t tx0 = X0 >> kTileShift, ty0 = Y0 >> kTileShift;
+  const int64_t wpr = g.mtx / 32;
+  uint32_t* m = g.wmask + p * g.mty * wpr;
   while (bits) {
     const int b = __builtin_ctz(bits);
     bits &= bits - 1u;
     int64_t tx = tx0 + b / 3, ty = ty0 + b % 3;
-    tx -= tx >= g.ntx ? g.ntx : 0;
-    ty -= ty >= g.nty ? g.nty : 0;
+    tx -= tx >= g.mtx ? g.mtx : 0;
+    ty -= ty >= g.mty ? g.mty : 0;
     atomicOr(m + ty * wpr + tx / 32, 1u << (unsigned)(tx % 32));
   }
 }
@@ -568,21 +583,20 @@ __device__ __forceinline__ void perm_decode(uint64_t e, const RowMap& m, int64_t
   }
 }
 
-// Tile key of a footprint origin: tile-major, key = ((iy0 / T) ntx + ix0 / T)
-// ntw + iw0, so the w layers of one uv tile are adjacent in the tile-sorted
+// Tile key of a footprint origin: tile-major, key = ((iy0 / TY) ntx + ix0 / TX)
+// ntw + iw0 (the work tile's edges are powers of two: shifts), so the w layers of one uv tile are adjacent in the tile-sorted
 // stream and a w-stacking plane's work units (layers p - W + 1 .. p of a tile)
 // are contiguous ranges (2-D: ntw = 1, key = tile).
 __device__ __forceinline__ int64_t tile_key(int64_t ix0, int64_t iy0, int64_t iw0, const GridGeometry& g) {
-  // ix0, iy0 in [0, 2^31) after wrapping: unsigned division
-  return ((int64_t)((uint32_t)iy0 / (uint32_t)kTile) * g.ntx + (int64_t)((uint32_t)ix0 / (uint32_t)kTile)) * g.ntw +
-         iw0;
+  // ix0, iy0 in [0, 2^31) after wrapping
+  return ((int64_t)((uint32_t)iy0 >> g.ty_shift) * g.ntx + (int64_t)((uint32_t)ix0 >> g.tx_shift)) * g.ntw + iw0;
 }
 
-// Grid origin of a tile key's T x T tile.
+// Grid origin of a tile key's work tile.
 __device__ __forceinline__ void tile_origin(int64_t key, const GridGeometry& g, int64_t* X0, int64_t* Y0) {
   const int64_t t = key / g.ntw;
-  *X0 = (t % g.ntx) * kTile;
-  *Y0 = ((t / g.ntx) % g.nty) * kTile;
+  *X0 = (t % g.ntx) << g.tx_shift;
+  *Y0 = ((t / g.ntx) % g.nty) << g.ty_shift;
 }
 
 // One visibility's linear-feed correlations (XX, XY, YX, YY) in complex64:

@@ -289,8 +289,11 @@ __global__ __launch_bounds__(kOrderThreads, 8) void order_kernel(const uint8_t* 
 
 // Row phases apply when the entries have a bit to spare (bit 31 of dense
 // entries, bit 63 of ragged ones - the packed (index, row, channel) form must
-// leave it free) and the lane scatter's support gives a full cycle (dP = (T +
-// W - 1) mod 16 odd)
+// leave it free) and the lane scatter's support gives a full cycle (dP = (TY +
+// W - 1) mod 16 odd). The work tile's TY is 32 or 64, so the row stride P = TY
+// + W - 1 has one residue mod 16 and mod 32 whatever the plan's tile: the
+// classes, dP and this test do not depend on it.
+static_assert(kTile % 32 == 0, "P mod 32 is the same for every work tile edge");
 bool order_phases_ok(const RowMap& m, int support) {
   const int wide = m.delta == nullptr ? 0 : (m.pk_cbits ? 2 : 1);
   const bool spare = wide == 0 ? m.nvis < ((int64_t)1 << 31)
@@ -328,11 +331,13 @@ hipError_t launch_scatter(const ScatterLaunch& a, hipStream_t s) {
   if (a.packed && a.vis_dtype != CIP_C64 && a.vis_dtype != CIP_POL4I) return hipErrorInvalidValue;
   const dim3 gd((unsigned)a.nchunks);
   // three blocks per CU: each needs > 160 KB / 4 of LDS (static sub-grid +
-  // this pad); the 256-thread lane kernels only (plane groups run 512)
+  // this pad); the 256-thread lane kernels only (plane groups and the 64 x 64
+  // work tile run 512: two of its fp64 sub-grids fill the LDS, so the kernels
+  // of another stream get what its 128-VGPR waves leave of the register file)
   unsigned pad = 0;
-  if (a.share_cus && a.group == 1 && a.support <= 16) {
-    const unsigned P = (unsigned)(kTile + a.support - 1);
-    const unsigned stat = P * P * (a.packed ? 8u : 16u) + 64u;
+  const unsigned TX = 1u << a.g.tx_shift, TY = 1u << a.g.ty_shift;
+  if (a.share_cus && a.group == 1 && a.support <= 16 && TX * TY <= 2u * kTile * kTile) {
+    const unsigned stat = (TX + a.support - 1) * (TY + a.support - 1) * (a.packed ? 8u : 16u) + 64u;
     // 3 blocks per CU: the optimum of 2 / 3 / 4 (profiles/r03_ab_scatter_share.txt, r05z_ab_share_blocks.txt)
     const unsigned nb = 3u;
     const unsigned need = 160u * 1024u / (nb + 1u) + 256u;

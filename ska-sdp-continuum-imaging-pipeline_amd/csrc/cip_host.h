@@ -88,7 +88,8 @@ struct PlanResult {
   Chunk* chunks = nullptr;
   void* perm = nullptr;  // bank-class ordered visibility stream (perm_encode entries), or NULL
   bool phases = false;   // perm's entries carry row phases (RowMap::row_phase for the scatter)
-  uint32_t* dmask = nullptr;  // grid tiles the scatter writes, per plane (bit-packed, ntx / 32 words per tile row)
+  uint32_t* dmask = nullptr;  // 32-cell grid tiles the scatter writes, per plane (bit-packed, mtx / 32 words per tile row)
+  int tx_shift = kTileShift, ty_shift = kTileShift;  // the work tile the plan was made on (GridGeometry's)
 };
 
 struct Workspace {
@@ -184,7 +185,14 @@ int end_call(const Call& c);
 // ---- cip_params.hip ----
 int choose(int64_t npix_x, int64_t npix_y, double px, double py, double epsilon, int support, int do_wstacking,
            double wmin, double wmax, cip_gridder_params* out);
-GridGeometry geometry(const cip_gridder_params& p, double px, double py);
+// the scatter's work tile as shifts (GridGeometry::tx_shift / ty_shift); 32 x 32 by default
+struct TileShape {
+  int tx_shift = kTileShift, ty_shift = kTileShift;
+};
+// the larger work tile of the selection rule (scatter_tile_shape)
+constexpr TileShape kDefaultScatterTile{6, 6};
+GridGeometry geometry(const cip_gridder_params& p, double px, double py, TileShape t = TileShape());
+TileShape scatter_tile_shape(const cip_gridder_params& p, bool packed, bool eligible);
 int correction_vectors(Workspace* ws, const GridGeometry& g, int64_t npix_x, int64_t npix_y, hipStream_t s,
                        double** cx_out, double** cy_out);
 int w_correction_table(Workspace* ws, const cip_gridder_params& prm, const GridGeometry& g, hipStream_t s,
@@ -204,6 +212,7 @@ bool ragged_pack();
 bool row_phases();
 int wstack_group_cap();
 int flush_store_mode();
+int scatter_tile_force();
 bool grid_f32_enabled();
 bool wacc_f32_enabled();
 bool fft_rowskip();
@@ -244,6 +253,7 @@ struct PlanRequest {
   const RaggedRows* ragged = nullptr;
   bool reuse = false;      // CIP_REUSE_PLAN
   bool want_group = true;  // w-plane groups (wstack_group); false: one plane per work unit
+  bool wide_tile = false;  // a cip_ms2dirty* call: the plan may use a larger work tile (scatter_tile_shape)
   int64_t plane_begin = 0, plane_end = -1;
 };
 // cip_planner.hip. grid_out (may be NULL): also takes the workspace grid and

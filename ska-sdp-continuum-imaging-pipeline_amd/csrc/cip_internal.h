@@ -82,10 +82,11 @@ hipError_t launch_radix_scatter(const uint32_t* keys, const uint64_t* vals, int6
 // kmask: the key bits that hold the tile (kRunKeyMask under RowMap::pk_runs, else all)
 hipError_t launch_tile_offsets(const uint32_t* keys, int64_t nruns, int64_t ntiles, int64_t* tile_run_off,
                                uint32_t kmask, hipStream_t s);
-// per grid plane (nplanes x ntx x nty bytes); bits (optional, ntx % 32 ==
-// 0): the masks bit-packed, ntx / 32 words per tile row, ntx nty / 32 per plane
-hipError_t launch_dirty_mask(const int64_t* tile_vis, int64_t ntx, int64_t nty, int64_t ntw, int support,
-                             int64_t nplanes, uint8_t* mask, uint32_t* bits, hipStream_t s);
+// per grid plane (nplanes x mtx x mty bytes, 32-cell mask tiles, from the
+// plan's work tiles); bits (optional, mtx % 32 == 0): the masks bit-packed,
+// mtx / 32 words per tile row, mtx mty / 32 per plane
+hipError_t launch_dirty_mask(const int64_t* tile_vis, const GridGeometry& g, uint8_t* mask, uint32_t* bits,
+                             hipStream_t s);
 hipError_t launch_tile_vis(const int64_t* run_goff, const int64_t* tile_run_off, int64_t ntiles,
                            int64_t* tile_vis_off, int64_t* tile_vis, hipStream_t s);
 // full_first: full chunks of every tile before the partial ones (chunk_off

@@ -106,7 +106,7 @@ static int plane_to_dirty(const DirtyStage& st, const GridGeometry& g, int64_t p
   const bool eo = st.fast && fft_cols_eo(g.nv, st.npix_y, g.grid_f32 != 0, g.do_wstacking ? 1 : 0);
   if (st.fast) {
     if (!fft_rowskip()) rowbits = nullptr;
-    CIP_HIP_CHECK(launch_fft_rows(grid, g.nu, g.nv, st.npix_x, st.tw_u, st.fft_h, dmask, g.ntx, rowbits != nullptr,
+    CIP_HIP_CHECK(launch_fft_rows(grid, g.nu, g.nv, st.npix_x, st.tw_u, st.fft_h, dmask, g.mtx, rowbits != nullptr,
                                   g.grid_f32 != 0, eo, s));
   } else if (hipfftExecZ2Z(st.plan, (hipfftDoubleComplex*)grid, (hipfftDoubleComplex*)grid, HIPFFT_BACKWARD) !=
              HIPFFT_SUCCESS) {
@@ -205,8 +205,8 @@ static int grid_accumulate(PlanRequest rq, const GridTarget& t, void* hip_stream
     // the strip's dirty-tile bits for its masked pass A: the tiles this
     // call's flush writes (GridGeometry::wmask, exact) + the tile rows
     // receiving the previous rank's halo (after the scatter, below)
-    if (pp.g.ntx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
-    const int64_t words = pp.g.nplanes * pp.g.nty * (pp.g.ntx / 32);
+    if (pp.g.mtx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
+    const int64_t words = pp.g.nplanes * pp.g.mty * (pp.g.mtx / 32);
     wmask = buf<uint32_t>(ws, "strip_wmask", words);
     if (!wmask) return CIP_ENOMEM;
     CIP_HIP_CHECK(hipMemsetAsync(wmask, 0, sizeof(uint32_t) * words, s));
@@ -257,6 +257,7 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
   const bool normalise = (flags & CIP_NORMALISE) != 0;
   const bool packed = rq.packed = (flags & CIP_ACC_SINGLE) != 0;
   rq.reuse = (flags & CIP_REUSE_PLAN) != 0;
+  rq.wide_tile = true;
   if (flags & CIP_PSF) {
     rq.vis = nullptr;
     if (rq.vis_dtype != CIP_POL4I) rq.vis_dtype = CIP_C64;
@@ -368,8 +369,8 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
   // unless cip_ms2dirty_wplanes); an empty range leaves a zero image
   const int64_t p_lo = g.plane_lo, p_hi = g.plane_hi;
   if (p_lo >= p_hi) CIP_HIP_CHECK(hipMemsetAsync(dirty_out, 0, sizeof(double) * npix_x * npix_y, s));
-  const int64_t rb_stride = (g.nty + 31) / 32;
-  const uint32_t* rowbits0 = dmask ? dmask + g.nplanes * (g.ntx * g.nty / 32) : nullptr;
+  const int64_t rb_stride = (g.mty + 31) / 32;
+  const uint32_t* rowbits0 = dmask ? dmask + g.nplanes * (g.mtx * g.mty / 32) : nullptr;
   if (const int jr = plan_join.join(); jr != CIP_OK) return jr;
   // the packed class's w planes accumulate in a float image (its own
   // precision, one rounding per plane; the final correction writes the fp64
@@ -390,7 +391,7 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
     if (rc != CIP_OK) return rc;
     for (int64_t p = std::max(q * G, p_lo); p < std::min<int64_t>(q * G + G, p_hi); ++p) {
       double* plane_p = (double*)((char*)grid + (size_t)(p - q * G) * (size_t)plane_elems * cell_bytes);
-      const uint32_t* dm = dmask ? dmask + p * (g.ntx * g.nty / 32) : nullptr;
+      const uint32_t* dm = dmask ? dmask + p * (g.mtx * g.mty / 32) : nullptr;
       const uint32_t* rbp = rowbits0 ? rowbits0 + p * rb_stride : nullptr;
       rc = plane_to_dirty(st, g, p, plane_p, wacc ? (double*)wacc : dirty_out, s, dm, normalise ? pp.red : nullptr,
                           rbp, p == p_lo, wacc != nullptr);

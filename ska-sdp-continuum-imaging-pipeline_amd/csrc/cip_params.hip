@@ -180,7 +180,7 @@ int choose(int64_t npix_x, int64_t npix_y, double px, double py, double epsilon,
   return CIP_OK;
 }
 
-GridGeometry geometry(const cip_gridder_params& p, double px, double py) {
+GridGeometry geometry(const cip_gridder_params& p, double px, double py, TileShape t) {
   GridGeometry g;
   g.nu = p.nu;
   g.nv = p.nv;
@@ -192,9 +192,13 @@ GridGeometry geometry(const cip_gridder_params& p, double px, double py) {
   g.dw = p.dw;
   g.inv_dw = 1.0 / p.dw;
   g.nplanes = p.nplanes;
-  g.tile = p.tile;
-  g.ntx = (p.nu + p.tile - 1) / p.tile;
-  g.nty = (p.nv + p.tile - 1) / p.tile;
+  g.tile = kTile;
+  g.tx_shift = t.tx_shift;
+  g.ty_shift = t.ty_shift;
+  g.ntx = (p.nu + ((int64_t)1 << t.tx_shift) - 1) >> t.tx_shift;
+  g.nty = (p.nv + ((int64_t)1 << t.ty_shift) - 1) >> t.ty_shift;
+  g.mtx = (p.nu + kTile - 1) / kTile;
+  g.mty = (p.nv + kTile - 1) / kTile;
   g.ntw = p.do_wstacking ? (p.nplanes - p.support + 1) : 1;
   g.transposed = 0;
   g.row0 = 0;
@@ -289,6 +293,26 @@ int wstack_group(const GridGeometry& g, bool packed) {
   return G;
 }
 
+// The 2-D lane scatter's work tile (the one selection rule). A larger tile
+// makes longer row slices - fewer runs for the planner's sort, scans and order
+// pass, fewer partly used lines in the scatter's gathers, less halo per cell in
+// the flush - but fewer, larger work units: only where all of
+// `eligible` holds (prepare(): a cip_ms2dirty* call, 2-D, dense rows, the
+// ordered stream) and the support's sub-grids fit (scatter_tile_fits); unforced,
+// also only on grids of whole 64-cell tiles with enough of them to fill the
+// CUs (nu nv >= 2048^2: smaller grids keep their 32 x 32 plans). Everything
+// else - w-stacking, cip_grid_*, ragged slices, the large supports, predict -
+// plans 32 x 32. CIP_SCATTER_TILE forces a shape wherever it is eligible and fits.
+TileShape scatter_tile_shape(const cip_gridder_params& p, bool packed, bool eligible) {
+  const TileShape t32;
+  if (!eligible || p.do_wstacking || p.support > 16) return t32;
+  const int force = scatter_tile_force();
+  TileShape t = force ? TileShape{5 + (force >> 1), 5 + (force & 1)} : kDefaultScatterTile;
+  if (force == 4) t = t32;
+  if (!force && (p.nu % 64 != 0 || p.nv % 64 != 0 || p.nu * p.nv < (int64_t)2048 * 2048)) return t32;
+  return scatter_tile_fits(p.support, packed, 1 << t.tx_shift, 1 << t.ty_shift) ? t : t32;
+}
+
 // ----------------------------------------------------------- switches ----
 // Every CIP_* environment switch of the library (DESIGN.md lists them with
 // the tests that use them). Unset means the default; a value whose first
@@ -358,6 +382,22 @@ bool order_classes32() {
     return e && e[0] == '3';
   }();
   return on;
+}
+// CIP_SCATTER_TILE=32 / 64x32 / 32x64 / 64: the 2-D lane scatter's work tile
+// wherever a call is eligible for one and it fits (scatter_tile_shape; A/B
+// runs and the tile tests at small sizes); unset: by the rule. Returns 0
+// unset, 4 for 32, else (x edge is 64) * 2 + (y edge is 64).
+int scatter_tile_force() {
+  static const int v = [] {
+    const char* e = env("CIP_SCATTER_TILE");
+    if (!e) return 0;
+    if (!strcmp(e, "32")) return 4;
+    if (!strcmp(e, "64x32")) return 2;
+    if (!strcmp(e, "32x64")) return 1;
+    if (!strcmp(e, "64") || !strcmp(e, "64x64")) return 3;
+    return 0;
+  }();
+  return v;
 }
 #undef CIP_SWITCH
 

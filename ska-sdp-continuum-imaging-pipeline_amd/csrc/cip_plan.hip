@@ -243,7 +243,8 @@ __device__ __forceinline__ void place_body(const double* __restrict__ uvw, const
   constexpr bool ragged = RM == 2;
   constexpr bool rowwave = RM == 1;
   const int64_t nseg = (nvis + 63) / 64;
-  const int P = kTile + g.support - 1;
+  // the sub-grid's row stride of the plan's work tile (TY + W - 1)
+  const int P = (1 << g.ty_shift) + g.support - 1;
   // block b owns segments [64 b, 64 b + 64): wave w takes every 4th
   const int64_t seg_end = (blk + 1) * kPlaceSegs < nseg ? (blk + 1) * kPlaceSegs : nseg;
   // (row, channel) of the lane's visibility, advanced by 256 visibilities per
@@ -336,13 +337,15 @@ __device__ __forceinline__ void place_body(const double* __restrict__ uvw, const
       if (g.do_wstacking) feeds = (iw0 + g.support > g.plane_lo) & (iw0 < g.plane_hi);
       // the tile key modulo 2^32 (keys are < 2^32 - 1)
       // tile_key(): tile-major, the w layers of a uv tile adjacent
-      const uint32_t key = (valid & ok & feeds) ? ((((uint32_t)iy0 / (uint32_t)kTile) * (uint32_t)g.ntx +
-                                            (uint32_t)ix0 / (uint32_t)kTile) *
+      const uint32_t key = (valid & ok & feeds) ? ((((uint32_t)iy0 >> g.ty_shift) * (uint32_t)g.ntx +
+                                            ((uint32_t)ix0 >> g.tx_shift)) *
                                                (uint32_t)g.ntw +
                                            (uint32_t)iw0)
                                         : kNoKey;
       bad_any = bad_any | (valid & !ok);
-      // the bank class ((ix0 % T) P + iy0 % T) % 32 (T = 32)
+      // the bank class ((ix0 % TX) P + iy0 % TY) % 32: the sub-grid element of
+      // the footprint origin (TX P and TY are multiples of 32, so the whole
+      // coordinates give the same residue)
       if (vis_class && valid)
         vis_class[i] = ok ? (uint8_t)(((unsigned)ix0 * (unsigned)P + (unsigned)iy0) & 31u) : (uint8_t)0;
       // the previous lane's key and row: DPP wave_shr:1 (a VALU move; __shfl_up
@@ -509,8 +512,9 @@ __device__ __forceinline__ void place_rows64_body(const double* __restrict__ uvw
   const int nseg = (int)(m.nvis / 64);  // nvis = nrow nchan: whole segments
   const int blk32 = (int)blk;
   const int seg_end = (blk32 + 1) * kPlaceSegs < nseg ? (blk32 + 1) * kPlaceSegs : nseg;
-  const unsigned P = (unsigned)(kTile + g.support - 1);
+  const unsigned P = (unsigned)((1 << g.ty_shift) + g.support - 1);  // the work tile's row stride
   const uint32_t ntx = (uint32_t)g.ntx, ntw = (uint32_t)g.ntw;
+  const int txs = g.tx_shift, tys = g.ty_shift;
   constexpr bool wstack = WS;
   // the wave's first segment: row r, channels c0 .. c0 + 63; then 256
   // visibilities per step
@@ -546,7 +550,7 @@ __device__ __forceinline__ void place_rows64_body(const double* __restrict__ uvw
     const bool ok = place_origin<WS ? 1 : 0>(u, v, w, f, g, &ix0, &iy0, &iw0);
     bool feeds = true;
     if constexpr (WS) feeds = (iw0 + g.support > g.plane_lo) & (iw0 < g.plane_hi);
-    const uint32_t tk = ((uint32_t)iy0 / (uint32_t)kTile) * ntx + (uint32_t)ix0 / (uint32_t)kTile;
+    const uint32_t tk = ((uint32_t)iy0 >> tys) * ntx + ((uint32_t)ix0 >> txs);
     const uint32_t key = (ok & feeds) ? (WS ? tk * ntw + (uint32_t)iw0 : tk) : kNoKey;
     bad_any |= __ballot(!ok);
     if (vis_class)
@@ -908,14 +912,15 @@ __global__ void tile_vis_kernel(const int64_t* run_goff, const int64_t* tile_run
   if (t < ntiles) tile_vis[t] = run_goff[tile_run_off[t + 1]] - a;
 }
 
-// Dirty-tile masks of the HBM grid, one per grid plane (nplanes x ntx x nty
-// bytes, zeroed by the caller): tile (tx, ty) of plane p is written by the
-// scatter's flush when a visibility of a tile layer feeding p (w-stacking:
-// layers p - W + 1 .. p; 2-D: the one layer) lands in it or, through the
-// (T + W - 1)^2 sub-grid's halo, in one of its -x, -y or -x-y neighbours
-// within the halo's reach (periodic grid).
-__global__ void dirty_mask_kernel(const int64_t* __restrict__ tile_vis, int64_t ntx, int64_t nty, int64_t ntw,
-                                  int support, int64_t nplanes, uint8_t* __restrict__ mask) {
+// Dirty-tile masks of the HBM grid, one per grid plane (nplanes x mtx x mty
+// bytes of 32-cell mask tiles, zeroed by the caller): a work tile (tx, ty) of
+// plane p visited by a visibility of a tile layer feeding p (w-stacking:
+// layers p - W + 1 .. p; 2-D: the one layer) marks every mask tile its
+// (TX + W - 1) x (TY + W - 1) sub-grid reaches (periodic grid) - the scatter's
+// flush writes no other.
+__global__ void dirty_mask_kernel(const int64_t* __restrict__ tile_vis, GridGeometry g, uint8_t* __restrict__ mask) {
+  const int64_t ntx = g.ntx, nty = g.nty, ntw = g.ntw, nplanes = g.nplanes;
+  const int support = g.support;
   const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nt = ntx * nty;
   if (id >= nt * nplanes) return;
@@ -928,14 +933,15 @@ __global__ void dirty_mask_kernel(const int64_t* __restrict__ tile_vis, int64_t 
   bool touched = false;
   for (int64_t w = lo; w <= hi && !touched; ++w) touched = tile_vis[t * ntw + w] > 0;  // tile-major keys
   if (!touched) return;
-  const int64_t tx = t % ntx, ty = t / ntx;
-  uint8_t* m = mask + p * nt;
-  // the sub-grid's cells reach T + W - 2 past the tile origin: h more tiles
-  // per axis (1 for W <= T + 1, 2 for the large supports up to 64)
-  const int h = (kTile + support - 2) / kTile;
-  for (int dy = 0; dy <= h; ++dy) {
-    const int64_t yy = (ty + dy) % nty;
-    for (int dx = 0; dx <= h; ++dx) m[yy * ntx + (tx + dx) % ntx] = 1;  // idempotent stores: no atomics needed
+  uint8_t* m = mask + p * g.mtx * g.mty;
+  // the sub-grid's cells reach TX + W - 2 (TY + W - 2) past the tile origin,
+  // a multiple of the mask unit: hx (hy) more mask tiles (1 for T = 32 and W <=
+  // 33, 2 for its large supports up to 64 and for a 64-cell edge)
+  const int64_t mx0 = (t % ntx) << (g.tx_shift - kTileShift), my0 = (t / ntx) << (g.ty_shift - kTileShift);
+  const int hx = ((1 << g.tx_shift) + support - 2) >> kTileShift, hy = ((1 << g.ty_shift) + support - 2) >> kTileShift;
+  for (int dy = 0; dy <= hy; ++dy) {
+    const int64_t yy = (my0 + dy) % g.mty;
+    for (int dx = 0; dx <= hx; ++dx) m[yy * g.mtx + (mx0 + dx) % g.mtx] = 1;  // idempotent stores: no atomics needed
   }
 }
 
@@ -972,18 +978,17 @@ __global__ void row_bits_kernel(const uint32_t* __restrict__ bits, int64_t ntx, 
   rows[id] = out;
 }
 
-hipError_t launch_dirty_mask(const int64_t* tile_vis, int64_t ntx, int64_t nty, int64_t ntw, int support,
-                             int64_t nplanes, uint8_t* mask, uint32_t* bits, hipStream_t s) {
-  const int64_t n = ntx * nty * nplanes;
-  dirty_mask_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(tile_vis, ntx, nty, ntw, support,
-                                                                           nplanes, mask);
+hipError_t launch_dirty_mask(const int64_t* tile_vis, const GridGeometry& g, uint8_t* mask, uint32_t* bits,
+                             hipStream_t s) {
+  const int64_t n = g.ntx * g.nty * g.nplanes;  // one thread per work tile and plane
+  dirty_mask_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(tile_vis, g, mask);
   if (bits) {
-    if (ntx % 32 != 0) return hipErrorInvalidValue;
-    const int64_t nw = n / 32;
+    if (g.mtx % 32 != 0) return hipErrorInvalidValue;
+    const int64_t nw = g.mtx * g.mty * g.nplanes / 32;
     pack_mask_kernel<<<dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s>>>(mask, nw, bits);
     // the row bits follow the tile bits (dirty_bits_words())
-    const int64_t nr = (nty + 31) / 32 * nplanes;
-    row_bits_kernel<<<dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, s>>>(bits, ntx, nty, nplanes, bits + nw);
+    const int64_t nr = (g.mty + 31) / 32 * g.nplanes;
+    row_bits_kernel<<<dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, s>>>(bits, g.mtx, g.mty, g.nplanes, bits + nw);
   }
   return hipGetLastError();
 }

@@ -123,12 +123,13 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
   CIP_ALLOC(scan_tmp2, int64_t, "scan_tmp2", scan_tmp_elems(nruns + 1))
   CIP_HIP_CHECK(scan_run_offsets(runs, nruns, run_goff, scan_tmp2, mp.pk_runs ? kin : nullptr, s));
   CIP_HIP_CHECK(launch_tile_vis(run_goff, tile_run_off, ntiles, tile_vis_off, tile_vis, s));
-  if (g.ntx % 32 == 0 && grid_mask()) {
-    CIP_ALLOC(dmask, uint8_t, "dirty_mask", g.ntx * g.nty * g.nplanes)
+  if (g.mtx % 32 == 0 && grid_mask()) {
+    // 32-cell mask tiles, whatever the plan's work tile
+    CIP_ALLOC(dmask, uint8_t, "dirty_mask", g.mtx * g.mty * g.nplanes)
     // tile bits, then tile-row bits (row_bits_kernel), per plane
-    CIP_ALLOC(dbits, uint32_t, "dirty_bits", g.ntx * g.nty / 32 * g.nplanes + (g.nty + 31) / 32 * g.nplanes)
-    CIP_HIP_CHECK(hipMemsetAsync(dmask, 0, (size_t)(g.ntx * g.nty * g.nplanes), s));
-    CIP_HIP_CHECK(launch_dirty_mask(tile_vis, g.ntx, g.nty, g.ntw, g.support, g.nplanes, dmask, dbits, s));
+    CIP_ALLOC(dbits, uint32_t, "dirty_bits", g.mtx * g.mty / 32 * g.nplanes + (g.mty + 31) / 32 * g.nplanes)
+    CIP_HIP_CHECK(hipMemsetAsync(dmask, 0, (size_t)(g.mtx * g.mty * g.nplanes), s));
+    CIP_HIP_CHECK(launch_dirty_mask(tile_vis, g, dmask, dbits, s));
     pr->dmask = dbits;
   }
   // 2-D: the scatter's work units largest first (one tile layer, so the
@@ -284,8 +285,11 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
                                    rq.epsilon, (double)rq.support, (double)rq.do_wstacking, (double)packed,
                                    rq.given ? 1.0 : 0.0, rq.want_group ? 1.0 : 0.0, (double)rq.plane_begin,
                                    (double)rq.plane_end};
-  const bool reusing = rq.reuse && !ragged && rq.given == nullptr && ws->saved_valid && ws->saved_key == key;
-  const cip_gridder_params* given = reusing ? &ws->saved_p : rq.given;
+  // the saved plan's work tile is part of the match (below, once this call's
+  // own is known); a saved 32 x 32 plan - a predict's - also serves an invert
+  // whose rule would pick a larger tile: it then runs the 32 x 32 scatter
+  const bool reusable = rq.reuse && !ragged && rq.given == nullptr && ws->saved_valid && ws->saved_key == key;
+  const cip_gridder_params* given = reusable ? &ws->saved_p : rq.given;
   double wmin = 0.0, wmax = 0.0;
   if (rq.do_wstacking && nrow > 0 && given == nullptr) {
     const int nb = 256;
@@ -309,7 +313,18 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
                           &out->p);
     if (rc != CIP_OK) return rc;
   }
-  out->g = geometry(out->p, rq.px, rq.py);
+  // the plan's work tile: larger than 32 x 32 only on the 2-D ordered-stream
+  // lane path of an invert (make_plan orders dense rows of < 2^32 visibilities)
+  const bool tile_ok = rq.wide_tile && !ragged && scatter_order() && m.nvis < ((int64_t)1 << 32);
+  TileShape shape = scatter_tile_shape(out->p, packed, tile_ok);
+  const TileShape saved_shape{ws->saved_plan.tx_shift, ws->saved_plan.ty_shift};
+  const bool saved32 = saved_shape.tx_shift == kTileShift && saved_shape.ty_shift == kTileShift;
+  const bool reusing =
+      reusable && ((saved_shape.tx_shift == shape.tx_shift && saved_shape.ty_shift == shape.ty_shift) || saved32);
+  // (a matching key with another tile - a predict after a 64-tile invert -
+  // plans afresh; 2-D only, where the saved parameters are this call's own)
+  if (reusing) shape = saved_shape;
+  out->g = geometry(out->p, rq.px, rq.py, shape);
   if (rq.plane_end >= 0) {
     // a range of the w-plane stack (cip_ms2dirty_wplanes)
     if (rq.plane_begin < 0 || rq.plane_begin > rq.plane_end || rq.plane_end > out->p.nplanes)
@@ -374,6 +389,8 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
     ws->saved_valid = false;
     rc = make_plan(ws, rq.uvw, fx, m, rq.vis, vis_dtype, rq.wgt, wgt_dtype, red, out->g, chunk_vis(packed, out->g.nu),
                    s, &out->plan, &maxabs, group);
+    out->plan.tx_shift = out->g.tx_shift;
+    out->plan.ty_shift = out->g.ty_shift;
     if (rc == CIP_OK && !ragged) {
       ws->saved_key = key;
       ws->saved_p = out->p;

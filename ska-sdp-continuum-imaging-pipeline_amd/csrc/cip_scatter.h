@@ -5,8 +5,10 @@
 // launch_scatter (cip_grid.hip) dispatches on W.
 //
 // Scatter design (DESIGN.md "Scatter kernel"): one 256-thread workgroup per
-// chunk (<= kChunkVis visibilities of one T x T grid tile, T = 32). The tile's
-// (T+W-1)^2 sub-grid lives in LDS as 64-bit fixed-point re/im pairs. Each lane
+// chunk (<= kChunkVis visibilities of one TX x TY grid tile; 32 x 32, and on
+// the 2-D ordered-stream path also 64 x 64 in 512-thread blocks, 64 x 32 and
+// 32 x 64 - the plan's work tile, GridGeometry::tx_shift / ty_shift). The tile's
+// (TX+W-1) x (TY+W-1) sub-grid lives in LDS as 64-bit fixed-point re/im pairs. Each lane
 // owns one visibility at a time (lane-per-visibility), evaluates the 2 x W
 // piecewise-polynomial kernel values, and adds its W x W taps with no-return
 // ds_add_u64. After the chunk the non-zero sub-grid cells are converted back
@@ -198,19 +200,18 @@ __device__ __forceinline__ unsigned long long* row_ptr(unsigned long long* b0, u
 // The packed class's visibility: fp32 kernel values and tap products (the
 // placement stays fp64, the planner's bit for bit). G > 1: the unit's G
 // planes as in grid_fetched.
-template <int W, bool WSTACK, int G>
+template <int W, bool WSTACK, int G, int TX, int TY>
 __device__ __forceinline__ void grid_fetched_packed(const VisFetch& f, const GridGeometry& g, int64_t plane,
                                                     int64_t X0, int64_t Y0, double fixed_scale,
                                                     unsigned long long* sub) {
-  constexpr int T = kTile;
-  constexpr int P = T + W - 1;
-  constexpr int S = P * P;
+  constexpr int P = TY + W - 1;
+  constexpr int S = (TX + W - 1) * P;
   if (f.wt == 0.0) return;
   int64_t ix0, iy0, iw0;
   double yu, yv, yw;
   if (!place_vis(f.u, f.v, f.w, f.fx, g, &ix0, &yu, &iy0, &yv, &iw0, &yw)) return;
   const int64_t lx = ix0 - X0, ly = iy0 - Y0;
-  if (lx < 0 || lx >= T || ly < 0 || ly >= T) return;  // never for a consistent plan
+  if (lx < 0 || lx >= TX || ly < 0 || ly >= TY) return;  // never for a consistent plan
   const double sc0 = f.wt * fixed_scale;
   const float vr0 = (float)(f.vr * sc0), vi0 = (float)(f.vi * sc0);
   float ku[W], kv[W];
@@ -258,13 +259,13 @@ __device__ __forceinline__ void grid_fetched_packed(const VisFetch& f, const Gri
 // One visibility onto the unit's sub-grid(s). G > 1 (w-stacking): the unit
 // grids planes plane .. plane + G - 1 at once (G sub-grids, S u64 apart), the
 // visibility placed and its u, v, w kernels evaluated once for all of them.
-template <int W, bool WSTACK, bool PACK, int G = 1>
+template <int W, bool WSTACK, bool PACK, int G = 1, int TX = kTile, int TY = kTile>
 __device__ __forceinline__ void grid_fetched(const VisFetch& f, const GridGeometry& g, int64_t plane, int64_t X0,
                                              int64_t Y0, double fixed_scale, unsigned long long* sub) {
-  constexpr int T = kTile;
-  constexpr int P = T + W - 1;
+  constexpr int P = TY + W - 1;       // the sub-grid's row stride: cell (lx, ly) at lx P + ly
+  constexpr int PP = (TX + W - 1) * P;  // its cells (the im plane follows the re plane)
   if constexpr (PACK) {
-    grid_fetched_packed<W, WSTACK, G>(f, g, plane, X0, Y0, fixed_scale, sub);
+    grid_fetched_packed<W, WSTACK, G, TX, TY>(f, g, plane, X0, Y0, fixed_scale, sub);
     return;
   }
   if (f.wt == 0.0) return;
@@ -272,9 +273,9 @@ __device__ __forceinline__ void grid_fetched(const VisFetch& f, const GridGeomet
   double yu, yv, yw;
   if (!place_vis(f.u, f.v, f.w, f.fx, g, &ix0, &yu, &iy0, &yv, &iw0, &yw)) return;
   const int64_t lx = ix0 - X0, ly = iy0 - Y0;
-  if (lx < 0 || lx >= T || ly < 0 || ly >= T) return;  // never for a consistent plan
+  if (lx < 0 || lx >= TX || ly < 0 || ly >= TY) return;  // never for a consistent plan
   if constexpr (G > 1) {
-    constexpr int S = P * P * (PACK ? 1 : 2);
+    constexpr int S = PP * (PACK ? 1 : 2);
     double kwv[W], ku[W], kv[W];
     eval_kernel<W>(yw, kwv);
     eval_kernel<W>(yu, ku);
@@ -317,7 +318,7 @@ __device__ __forceinline__ void grid_fetched(const VisFetch& f, const GridGeomet
             atomicAdd(bi0 + j, __builtin_bit_cast(unsigned long long, make_uint2((unsigned)bi, hi)));
           } else {
             atomicAdd(bi0 + j, br - kTapBias);
-            atomicAdd(bi0 + P * P + j, bi - kTapBias);
+            atomicAdd(bi0 + PP + j, bi - kTapBias);
           }
         }
       }
@@ -370,7 +371,7 @@ __device__ __forceinline__ void grid_fetched(const VisFetch& f, const GridGeomet
         atomicAdd(bi0 + j, __builtin_bit_cast(unsigned long long, make_uint2((unsigned)bi, hi)));
       } else {
         atomicAdd(bi0 + j, br - kTapBias);
-        atomicAdd(bi0 + P * P + j, bi - kTapBias);
+        atomicAdd(bi0 + PP + j, bi - kTapBias);
       }
     }
   }
@@ -378,17 +379,19 @@ __device__ __forceinline__ void grid_fetched(const VisFetch& f, const GridGeomet
 
 // Flush the touched cells of a work unit's sub-grid(s) to the HBM grid(s)
 // (called after the unit's last LDS atomic and a barrier).
-template <int W, bool PACK, int G, int NT>
+template <int W, bool PACK, int G, int NT, int TX = kTile, int TY = kTile>
 __device__ __forceinline__ void flush_subgrid(const unsigned long long* sub, const GridGeometry& g, int64_t plane,
                                               int64_t X0, int64_t Y0, const Chunk& ch, int store_private,
                                               double inv_scale, double* __restrict__ grid) {
-  constexpr int T = kTile;
-  constexpr int P = T + W - 1;
-  constexpr int S = P * P * (PACK ? 1 : 2);
+  constexpr int PX = TX + W - 1;  // sub-grid rows (x)
+  constexpr int P = TY + W - 1;   // cells per row (y): cell (lx, ly) at lx P + ly
+  constexpr int PP = PX * P;
+  constexpr int S = PP * (PACK ? 1 : 2);
+  static_assert((PX - 1) / kTile <= 2 && (P - 1) / kTile <= 2, "wmask_report: 3 x 3 mask tiles per sub-grid");
   // flush the touched cells of the sub-grid(s) to the fp64 HBM grid(s)
   // (lanes walk the HBM grid's contiguous axis: y, or x when it is stored
   // transposed for the pruned FFT); plane group: plane + k -> grid + k planes.
-  // A tile's cells [W - 1, T)^2 are written by its own units only (the
+  // A tile's cells [W - 1, TX) x [W - 1, TY) are written by its own units only (the
   // neighbours' sub-grids reach W - 1 cells into it): when this unit is the
   // tile's only one and the grid is zero (store_private: a cip_ms2dirty plane,
   // not an accumulating one; set on 16384^2+ planes), those cells are stored,
@@ -412,8 +415,8 @@ __device__ __forceinline__ void flush_subgrid(const unsigned long long* sub, con
   // transposed layout: ~45 VALU) is computed once, not once per plane - on the
   // reference call's G = 5 plane groups the per-plane form was ~1/3 of the
   // scatter's VALU instructions (7.25 -> 7.17 ms, profiles/r04_ab_flush_fused.txt)
-  for (int cell = threadIdx.x; cell < P * P; cell += NT) {
-    const int lcell = g.transposed ? (cell % P) * P + cell / P : cell;  // lx * P + ly
+  for (int cell = threadIdx.x; cell < PP; cell += NT) {
+    const int lcell = g.transposed ? (cell % PX) * P + cell / PX : cell;  // lx * P + ly
     unsigned long long sv[G];  // PACK: re * 2^32 + im
     unsigned long long si[G];  // !PACK: the im plane
     bool any = false;
@@ -423,7 +426,7 @@ __device__ __forceinline__ void flush_subgrid(const unsigned long long* sub, con
       si[k] = 0ull;
       if (G > 1 && (plane + k >= g.nplanes || plane + k < g.plane_lo || plane + k >= g.plane_hi)) continue;
       sv[k] = sub[k * S + lcell];
-      if constexpr (!PACK) si[k] = sub[k * S + P * P + lcell];
+      if constexpr (!PACK) si[k] = sub[k * S + PP + lcell];
       any |= (sv[k] | si[k]) != 0ull;
     }
     if (!any) continue;
@@ -437,8 +440,9 @@ __device__ __forceinline__ void flush_subgrid(const unsigned long long* sub, con
       continue;
     }
     const int lx = lcell / P, ly = lcell % P;
-    const bool priv = own && lx >= W - 1 && lx < T && ly >= W - 1 && ly < T;
-    const unsigned tbit = 1u << ((lx / T) * 3 + ly / T);
+    const bool priv = own && lx >= W - 1 && lx < TX && ly >= W - 1 && ly < TY;
+    // the 32-cell mask tile of the cell, relative to the origin's (wmask_report)
+    const unsigned tbit = 1u << ((lx / kTile) * 3 + ly / kTile);
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       if ((sv[k] | si[k]) == 0ull) continue;  // (also every plane outside the call's range)
@@ -485,21 +489,21 @@ __device__ __forceinline__ void flush_subgrid(const unsigned long long* sub, con
 // PERM: 0 = tile order through the row slices, 1 / 2 = the bank-class ordered
 // stream of dense (u32) / ragged (u64) entries. G: w planes per work unit
 // (w-stacking plane groups; G > 1 runs 512-thread blocks holding G sub-grids).
-template <int G>
+// A 64 x 64 work tile runs 512-thread blocks too: two of its sub-grids fill a
+// CU's LDS, and two such blocks are the 16 waves per CU of four 256-thread ones.
+template <int G, int TX = kTile, int TY = kTile>
 constexpr int scatter_threads() {
-  return G == 1 ? kScatterThreads : CIP_GROUP_THREADS;
+  return G == 1 && TX * TY <= 2 * kTile * kTile ? kScatterThreads : CIP_GROUP_THREADS;
 }
-template <int W, typename VisT, int WK, bool WSTACK, int PERM, bool PACK, int G = 1>
-__global__ __launch_bounds__(scatter_threads<G>(), CIP_SCATTER_WAVES) void scatter_kernel(
+template <int W, typename VisT, int WK, bool WSTACK, int PERM, bool PACK, int G = 1, int TX = kTile, int TY = kTile>
+__global__ __launch_bounds__((scatter_threads<G, TX, TY>()), CIP_SCATTER_WAVES) void scatter_kernel(
     const double* __restrict__ uvw, const double* __restrict__ fx, const VisT* __restrict__ vis,
     const void* __restrict__ wgt, RowMap m, const uint64_t* __restrict__ runs,
     const int64_t* __restrict__ run_goff, const int64_t* __restrict__ tile_run_off,
     const void* __restrict__ perm, const Chunk* __restrict__ chunks, int64_t chunk_begin, GridGeometry g,
     int64_t plane, double fixed_scale, double inv_scale, double* __restrict__ grid, int store_private) {
-  constexpr int T = kTile;
-  constexpr int P = T + W - 1;
-  constexpr int S = P * P * (PACK ? 1 : 2);
-  constexpr int NT = scatter_threads<G>();
+  constexpr int S = (TX + W - 1) * (TY + W - 1) * (PACK ? 1 : 2);
+  constexpr int NT = scatter_threads<G, TX, TY>();
   __shared__ unsigned long long sub[G * S];
   __shared__ int64_t s_voff[PERM ? 1 : kRunBatch + 1];
   __shared__ uint64_t s_run[PERM ? 1 : kRunBatch];
@@ -535,7 +539,8 @@ __global__ __launch_bounds__(scatter_threads<G>(), CIP_SCATTER_WAVES) void scatt
       const uint64_t pnn = perm_entry_t<kWide>(perm, hnn ? qnn : q);
       RawFetch<VisT, WK> nxt;
       fetch_raw<VisT, WK, kWide>(pn, uvw, fx, vis_ld, unit_vis, wgt, m, nxt);
-      grid_fetched<W, WSTACK, PACK, G>(from_raw<VisT, WK>(cur, unit_vis), g, plane, X0, Y0, fixed_scale, sub);
+      grid_fetched<W, WSTACK, PACK, G, TX, TY>(from_raw<VisT, WK>(cur, unit_vis), g, plane, X0, Y0, fixed_scale,
+                                               sub);
       cur = nxt;
       q = qn;
       have = hn;
@@ -566,7 +571,7 @@ __global__ __launch_bounds__(scatter_threads<G>(), CIP_SCATTER_WAVES) void scatt
         const bool hn = qn < bend;
         VisFetch nxt;
         if (hn) fetch_vis<VisT, WK>(qn, s_voff, s_run, nst, uvw, fx, vis, wgt, m, nxt);
-        grid_fetched<W, WSTACK, PACK, G>(cur, g, plane, X0, Y0, fixed_scale, sub);
+        grid_fetched<W, WSTACK, PACK, G, TX, TY>(cur, g, plane, X0, Y0, fixed_scale, sub);
         cur = nxt;
         q = qn;
         have = hn;
@@ -576,7 +581,7 @@ __global__ __launch_bounds__(scatter_threads<G>(), CIP_SCATTER_WAVES) void scatt
     }
   }
   __syncthreads();
-  flush_subgrid<W, PACK, G, NT>(sub, g, plane, X0, Y0, ch, store_private, inv_scale, grid);
+  flush_subgrid<W, PACK, G, NT, TX, TY>(sub, g, plane, X0, Y0, ch, store_private, inv_scale, grid);
 }
 
 // Plane groups G with a kernel instance: 1 .. 3 in both classes; the packed
@@ -596,6 +601,24 @@ inline hipError_t scatter_dispatch_ws(const ScatterLaunch& a, dim3 grid_dim, uns
   const int perm_form = !p.perm ? 0 : (p.m.delta != nullptr ? 2 : 1);
   auto launch = [&](auto pack) {
     constexpr bool PK = decltype(pack)::value;
+    // a plan on a larger work tile (scatter_tile_shape, cip_params.hip): the
+    // 2-D ordered stream of dense rows, one instance per shape that fits
+    if (a.g.tx_shift != kTileShift || a.g.ty_shift != kTileShift) {
+      if (ws || perm_form != 1 || a.group != 1) return hipErrorInvalidValue;
+      return dispatch_int<1, 2, 3>((a.g.tx_shift - kTileShift) * 2 + (a.g.ty_shift - kTileShift), hipErrorInvalidValue,
+                                   [&](auto sh) {
+        constexpr int TX = kTile << (decltype(sh)::value >> 1), TY = kTile << (decltype(sh)::value & 1);
+        if constexpr (!scatter_tile_fits(W, PK, TX, TY)) {
+          return hipErrorInvalidValue;  // (never planned: the selection falls back to 32 x 32)
+        } else {
+          scatter_kernel<W, VisT, WK, false, 1, PK, 1, TX, TY>
+              <<<grid_dim, dim3(scatter_threads<1, TX, TY>()), lds_extra, s>>>(
+                  p.uvw, p.fx, (const VisT*)p.vis, p.wgt, p.m, p.runs, p.run_goff, p.tile_run_off, p.perm, p.chunks,
+                  a.chunk_begin, a.g, a.plane, a.fixed_scale, 1.0 / a.fixed_scale, a.grid, a.store_private ? 1 : 0);
+          return hipGetLastError();
+        }
+      });
+    }
     // a group without an instance, and 2-D, run one plane per work unit
     const int group = ws && scatter_group_fits(W, PK, a.group) ? a.group : 1;
     return dispatch_int<0, 1, 2>(perm_form, hipErrorInvalidValue, [&](auto prm) {

@@ -271,10 +271,10 @@ __global__ void strip_mask_kernel(const uint32_t* __restrict__ dmask, int64_t np
 
 hipError_t launch_strip_mask(const uint32_t* dmask, const GridGeometry& g, int64_t row0, int64_t halo, uint32_t* out,
                              hipStream_t s) {
-  const int64_t wpr = g.ntx / 32;
-  const int64_t n = g.nplanes * g.nty * wpr;
+  const int64_t wpr = g.mtx / 32;
+  const int64_t n = g.nplanes * g.mty * wpr;
   if (n <= 0) return hipSuccess;
-  strip_mask_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(dmask, g.nplanes, g.nty, wpr, row0, halo,
+  strip_mask_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(dmask, g.nplanes, g.mty, wpr, row0, halo,
                                                                           g.nv, out);
   return hipGetLastError();
 }
@@ -413,7 +413,7 @@ int cip_strip_rows_masked(double* grid, const cip_gridder_params* params, int64_
   if (!grid || !H || !tile_bits) return set_error(CIP_EINVAL, "NULL grid, H or tile_bits");
   if (y0 < 0 || y1 > g.nv || y1 <= y0) return set_error(CIP_EINVAL, "row range outside the grid");
   if (row0 < 0 || row0 >= g.nv) return set_error(CIP_EINVAL, "row0 outside the grid");
-  if (g.ntx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
+  if (g.mtx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
   return strip_rows(hip_stream, grid, g, npix_x, y0, y1, H, tile_bits, row0);
 }
 
@@ -428,7 +428,7 @@ int cip_strip_rows_packed(double* grid, const cip_gridder_params* params, int64_
   if (row0 < 0 || row0 >= g.nv) return set_error(CIP_EINVAL, "row0 outside the grid");
   if (nlive < 0 || nlive > y1 - y0) return set_error(CIP_EINVAL, "nlive outside [0, y1 - y0]");
   if (nlive > 0 && !H) return set_error(CIP_EINVAL, "NULL H");
-  if (g.ntx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
+  if (g.mtx % 32 != 0) return set_error(CIP_EINVAL, "tile masks need nu / 32 to be a multiple of 32 tiles");
   return strip_rows(hip_stream, grid, g, npix_x, y0, y1, H, tile_bits, row0, row_slot, nlive);
 }
 

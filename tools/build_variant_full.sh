@@ -1,6 +1,6 @@
 #!/bin/bash
 # Experiment build of the whole library with extra defines:
-#   tools/build_variant_full.sh NAME "-DCIP_TILE=48 ..."
+#   tools/build_variant_full.sh NAME "-DCIP_ORDER_WINDOW=2048 ..."
 # output tools/variants/libcip_hip_NAME.so (select with CIP_HIP_LIB)
 set -e
 name=$1; defs=$2
