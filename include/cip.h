@@ -17,6 +17,9 @@
  *                         the reference leaves it to ducc0 on the CPU)
  *   cip_hogbom_clean   - the minor cycle between the two (Hogbom CLEAN on
  *                         the device; the reference has no deconvolution)
+ *   cip_imaging_weights, cip_weight_* - uniform and Briggs imaging weights
+ *                         from the weight density on the image's uv cells
+ *                         (the reference grids with the MS weights only)
  *   cip_choose_params  <- ducc0's internal parameter choice (grid size,
  *                         kernel support, w-planes), SURVEY.md 8(a) a4.1/a4.2
  *   cip_tile_runs      <- create_uvw_tile_mapping_sequential's per-row key and
@@ -229,6 +232,116 @@ int cip_hogbom_clean(double* residual_io, int64_t nx, int64_t ny,
                      int64_t batch, void* hip_stream, double* model_io,
                      int64_t* comp_index, double* comp_flux,
                      cip_clean_result* result_out);
+
+/* Imaging weights (uniform and Briggs / robust) on the device; no reference
+ * counterpart (the reference grids with the measurement set's weights only,
+ * invert.py:72-116, which is natural weighting). The operator is defined
+ * here, rounding included.
+ *
+ * Weighting grid. It belongs to an image of npix_x x npix_y pixels of
+ * pixsize_x, pixsize_y radians. With hx = npix_x / 2 and hy = npix_y / 2
+ * (integer division) the density is a DEVICE int64 array of shape
+ * (2 hx + 1, hy + 1), row-major, cell (iu, iv) stored at [iu + hx][iv];
+ * axis 0 <-> u <-> l as everywhere here. A cell is 1 / (npix pixsize)
+ * wavelengths wide: the field-of-view cell, not the oversampled gridding cell.
+ *
+ * Cell of visibility (r, c). Every operation is fp64, each one rounded, no
+ * contraction (no FMA):
+ *   wi = freq[c] / 299792458.0
+ *   su = uvw[r,0] * SX      sv = uvw[r,1] * SY
+ *        (SX = npix_x * pixsize_x, SY = npix_y * pixsize_y, host products)
+ *   x  = wi * su            y  = wi * sv
+ *   if (y < 0 || (y == 0 && x < 0)) { x = -x; y = -y; }
+ *        (the Hermitian fold to the v >= 0 half plane)
+ *   iu = floor(x + 0.5)     iv = floor(y + 0.5)
+ *   inside  <=>  x, y finite and |iu| <= hx and iv <= hy
+ *
+ * Fixed point. cip_weight_grid_init sets shift = 62 - B - E with B the least
+ * integer with nvis_max <= 2^B and E the least integer with wmax <= 2^E, so no
+ * sum of nvis_max weights <= wmax reaches 2^62; quantum = 2^-shift. A weight
+ * enters as q(w) = llrint(ldexp((double)w, shift)) (round-half-even; numpy:
+ * np.rint(np.ldexp(w, shift)).astype(np.int64)). The density is accumulated
+ * with 64-bit integer atomic adds: it is independent of arrival order, of
+ * chunking and of how many ranks' grids are summed, and identical inputs give
+ * identical bits. No floating-point atomics anywhere. */
+#define CIP_WEIGHT_NATURAL 0 /* the weights as they are (no library call needed) */
+#define CIP_WEIGHT_UNIFORM 1
+#define CIP_WEIGHT_BRIGGS 2
+typedef struct cip_weight_grid { /* HOST memory */
+  int64_t npix_x, npix_y;
+  double pixsize_x, pixsize_y;
+  double SX, SY;   /* npix_x * pixsize_x, npix_y * pixsize_y */
+  double wmax;     /* the bound the grid was made for: a larger weight is bad */
+  double quantum;  /* 2^-shift: the weight one density count stands for */
+  int32_t shift;
+  int32_t reserved;
+} cip_weight_grid;
+typedef struct cip_weight_info { /* HOST memory */
+  double sum_w;     /* (double)(sum of the density) * quantum */
+  double sum_d2;    /* sum over cells of D^2 */
+  double f2;        /* Briggs: (5 10^-robust)^2 / (sum_d2 / sum_w); else 0 */
+  double quantum;
+  int64_t n_added;  /* samples added to the density */
+  int64_t n_outside;/* samples with w > 0 outside the grid */
+  int64_t n_cells;  /* non-zero cells */
+} cip_weight_info;
+
+/* Host-only. CIP_EINVAL: wmax not finite or <= 0 (or so extreme that quantum
+ * is no normal double), nvis_max < 1, an npix < 1, a pixsize not finite or
+ * <= 0. */
+int cip_weight_grid_init(int64_t npix_x, int64_t npix_y, double pixsize_x,
+                         double pixsize_y, double wmax, int64_t nvis_max,
+                         cip_weight_grid* out);
+
+/* Adds the chunk's weights onto density_io (the caller zeroes it before the
+ * first chunk). uvw (nrow, 3) f64, freq (nchan) f64, wgt (nrow, nchan)
+ * f32 / f64, or NULL with CIP_NONE: all weights 1; DEVICE pointers. A sample
+ * with w == 0 is skipped and so is one whose cell lies outside. counts_out
+ * (HOST int64[3], may be NULL): samples added, samples with w > 0 outside the
+ * grid, bad samples (w < 0, NaN or > grid->wmax; never added). Any bad sample
+ * makes the call return CIP_ERANGE and the density contents are then
+ * unspecified. Synchronous on hip_stream (one readback); nrow == 0 is a no-op;
+ * nchan <= 65535 as elsewhere. */
+int cip_weight_density(const double* uvw, int64_t nrow, const double* freq,
+                       int64_t nchan, const void* wgt, int wgt_dtype,
+                       const cip_weight_grid* grid, void* hip_stream,
+                       int64_t* density_io, int64_t* counts_out);
+
+/* stats_out (HOST double[3]): sum_w = (double)(sum of density) * quantum (an
+ * exact integer sum: bit-defined); sum_d2 = sum_k D_k^2 with D_k =
+ * (double)density_k * quantum (a fixed-shape two-stage reduction without
+ * atomics: reproducible; only its summation order is the library's); the
+ * number of non-zero cells. Synchronous on hip_stream. */
+int cip_weight_stats(const int64_t* density, const cip_weight_grid* grid,
+                     void* hip_stream, double* stats_out);
+
+/* wgt_out[r, c] from wgt[r, c] (as cip_weight_density) and the sample's cell,
+ * D = (double)density[cell] * quantum, w64 = (double)w:
+ *   CIP_WEIGHT_UNIFORM: D > 0 ? w64 / D : 0
+ *   CIP_WEIGHT_BRIGGS:  w64 / (1.0 + D * f2)   (product, add and divide each
+ *                                               rounded)
+ * rounded once to out_dtype (CIP_F32 / CIP_F64). w == 0 or a cell outside the
+ * grid gives an exact 0. wgt_out may equal wgt when the dtypes match.
+ * Stream-ordered on hip_stream, no host wait. */
+int cip_weight_apply(const double* uvw, int64_t nrow, const double* freq,
+                     int64_t nchan, const void* wgt, int wgt_dtype,
+                     const int64_t* density, const cip_weight_grid* grid,
+                     int mode, double f2, void* hip_stream, void* wgt_out,
+                     int out_dtype);
+
+/* The one-shot call: a device max-reduction of wgt (exact), the grid for
+ * nvis_max = nrow nchan, the density in a grow-only workspace buffer (freed by
+ * cip_release_workspace), the statistics and the apply. Briggs: t = 5.0 *
+ * pow(10.0, -robust); f2 = (t * t) / (sum_d2 / sum_w) on the host (0 when
+ * sum_w is 0); robust must be finite. info_out (HOST, may be NULL). All-zero
+ * weights give all-zero output and CIP_OK; a negative or non-finite weight is
+ * CIP_ERANGE. Synchronous on hip_stream. */
+int cip_imaging_weights(const double* uvw, int64_t nrow, const double* freq,
+                        int64_t nchan, const void* wgt, int wgt_dtype,
+                        int64_t npix_x, int64_t npix_y, double pixsize_x,
+                        double pixsize_y, int mode, double robust,
+                        void* hip_stream, void* wgt_out, int out_dtype,
+                        cip_weight_info* info_out);
 
 /* cip_ms2dirty restricted to w planes [plane_begin, plane_end) of the
  * w-stacking stack (CIP_WSTACKING required): the multi-GPU split of ONE

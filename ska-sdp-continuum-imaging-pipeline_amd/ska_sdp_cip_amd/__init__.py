@@ -6,7 +6,8 @@ Public API mirrors `/root/reference/src/ska_sdp_cip/__init__.py:1-10`
 `dask_invert_measurement_set`, `__version__`) plus the drop-in gridder
 `ms2dirty` (replaces `ducc0.wgridder.ms2dirty`), its adjoint `dirty2ms`
 (`ducc0.wgridder.dirty2ms`; `predict.py` wraps it), the minor and major cycle
-built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`) and the
+built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), uniform
+and Briggs imaging weights (`weighting.py`, `cip_imaging_weights`) and the
 `uvw_tiling` package.
 """
 
@@ -22,6 +23,7 @@ from .invert import (  # noqa: E402
 )
 from .predict import device_residual, ducc_predict  # noqa: E402
 from .deconvolve import device_hogbom_clean, device_major_cycles, hogbom_clean  # noqa: E402
+from .weighting import WeightDensity, device_imaging_weights, imaging_weights  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -58,4 +60,7 @@ __all__ = [
     "hogbom_clean",
     "device_hogbom_clean",
     "device_major_cycles",
+    "imaging_weights",
+    "device_imaging_weights",
+    "WeightDensity",
 ]

@@ -40,6 +40,10 @@ CIP_CLEAN_NITER = 0
 CIP_CLEAN_THRESHOLD = 1
 CIP_CLEAN_EMPTY = 2
 CIP_CLEAN_DEFAULT_BATCH = 64
+CIP_WEIGHT_NATURAL = 0
+CIP_WEIGHT_UNIFORM = 1
+CIP_WEIGHT_BRIGGS = 2
+WEIGHTING_MODES = {"natural": CIP_WEIGHT_NATURAL, "uniform": CIP_WEIGHT_UNIFORM, "briggs": CIP_WEIGHT_BRIGGS}
 CLEAN_STOP_REASONS = {CIP_CLEAN_NITER: "niter", CIP_CLEAN_THRESHOLD: "threshold", CIP_CLEAN_EMPTY: "empty"}
 STOKES_CODES = {"I": 0, "Q": 1, "U": 2, "V": 3}
 
@@ -49,6 +53,11 @@ EXPORTED_SYMBOLS = (
     "cip_ms2dirty",
     "cip_dirty2ms",
     "cip_hogbom_clean",
+    "cip_weight_grid_init",
+    "cip_weight_density",
+    "cip_weight_stats",
+    "cip_weight_apply",
+    "cip_imaging_weights",
     "cip_ms2dirty_stokes_i",
     "cip_grid_plane",
     "cip_grid_layout",
@@ -122,6 +131,46 @@ class CleanResult(ctypes.Structure):
     ]
 
 
+class WeightGrid(ctypes.Structure):
+    """Mirror of `cip_weight_grid` (include/cip.h)."""
+
+    _fields_ = [
+        ("npix_x", ctypes.c_int64),
+        ("npix_y", ctypes.c_int64),
+        ("pixsize_x", ctypes.c_double),
+        ("pixsize_y", ctypes.c_double),
+        ("SX", ctypes.c_double),
+        ("SY", ctypes.c_double),
+        ("wmax", ctypes.c_double),
+        ("quantum", ctypes.c_double),
+        ("shift", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    @property
+    def density_shape(self) -> tuple:
+        """Shape of the grid's int64 density array: (2 hx + 1, hy + 1)."""
+        return (2 * (self.npix_x // 2) + 1, self.npix_y // 2 + 1)
+
+
+class WeightInfo(ctypes.Structure):
+    """Mirror of `cip_weight_info` (include/cip.h)."""
+
+    _fields_ = [
+        ("sum_w", ctypes.c_double),
+        ("sum_d2", ctypes.c_double),
+        ("f2", ctypes.c_double),
+        ("quantum", ctypes.c_double),
+        ("n_added", ctypes.c_int64),
+        ("n_outside", ctypes.c_int64),
+        ("n_cells", ctypes.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 _LIB = None
 
 _vp = ctypes.c_void_p
@@ -151,6 +200,14 @@ def lib() -> ctypes.CDLL:
                                 _vp, _vp, _i32, ctypes.POINTER(GridderParams)]
     so.cip_hogbom_clean.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _f64, _f64, _i64, _i64, _vp,
                                     _vp, _vp, _vp, ctypes.POINTER(CleanResult)]
+    so.cip_weight_grid_init.argtypes = [_i64, _i64, _f64, _f64, _f64, _i64, ctypes.POINTER(WeightGrid)]
+    so.cip_weight_density.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, ctypes.POINTER(WeightGrid), _vp, _vp,
+                                      ctypes.POINTER(ctypes.c_int64)]
+    so.cip_weight_stats.argtypes = [_vp, ctypes.POINTER(WeightGrid), _vp, ctypes.POINTER(ctypes.c_double)]
+    so.cip_weight_apply.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, ctypes.POINTER(WeightGrid), _i32, _f64,
+                                    _vp, _vp, _i32]
+    so.cip_imaging_weights.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _i64, _f64, _f64, _i32, _f64, _vp,
+                                       _vp, _i32, ctypes.POINTER(WeightInfo)]
     so.cip_ms2dirty_wplanes.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _f64, _f64,
                                         _f64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
     so.cip_ms2dirty_stokes_i.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _f64, _f64,
@@ -201,7 +258,8 @@ def lib() -> ctypes.CDLL:
                  "cip_grid_tiles", "cip_grid_tiles_strip", "cip_grid_tiles_strip_mask", "cip_strip_histogram",
                  "cip_strip_split", "cip_ms2dirty_wplanes", "cip_grid_to_dirty", "cip_strip_rows", "cip_strip_rows_masked", "cip_strip_cols", "cip_strip_cols_wplane", "cip_strip_wfinal", "cip_strip_pack_rows", "cip_strip_unpack_rows", "cip_strip_rows_packed", "cip_tile_runs",
                  "cip_stokes_i", "cip_stokes", "cip_facet_rephase", "cip_allreduce_grid", "cip_release_collectives",
-                 "cip_release_workspace", "cip_profile_enable", "cip_profile_last"):
+                 "cip_release_workspace", "cip_profile_enable", "cip_profile_last", "cip_weight_grid_init",
+                 "cip_weight_density", "cip_weight_stats", "cip_weight_apply", "cip_imaging_weights"):
         getattr(so, name).restype = ctypes.c_int
     _LIB = so
     return so
@@ -227,6 +285,15 @@ def choose_params(npix_x: int, npix_y: int, pixsize_x: float, pixsize_y: float,
     check(lib().cip_choose_params(int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y),
                                   float(epsilon), int(support or 0), int(bool(do_wstacking)),
                                   float(wmin), float(wmax), ctypes.byref(out)))
+    return out
+
+
+def weight_grid(npix_x: int, npix_y: int, pixsize_x: float, pixsize_y: float, wmax: float,
+                nvis_max: int) -> WeightGrid:
+    """The weighting grid and fixed-point scale of `cip_weight_grid_init` (host-only)."""
+    out = WeightGrid()
+    check(lib().cip_weight_grid_init(int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y), float(wmax),
+                                     int(nvis_max), ctypes.byref(out)))
     return out
 
 

@@ -20,6 +20,7 @@ from . import _lib
 from .gridder import _check_device_tensor, _require_gpu, _to_device, device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .predict import device_residual
+from .weighting import device_imaging_weights
 
 try:
     import torch
@@ -168,6 +169,8 @@ def device_major_cycles(
     epsilon: float = EPSILON,
     do_wstacking: bool = DO_WSTACKING,
     support: Optional[int] = None,
+    weighting: str = "natural",
+    robust: float = 0.0,
 ):
     """
     Major cycles on device-resident data (an `npix` x `npix` image with pixels
@@ -183,6 +186,11 @@ def device_major_cycles(
     discarded in favour of the re-inverted one. The loop ends early once a
     cycle starts at or below `threshold`.
 
+    `weighting` ("natural", "uniform" or "briggs" with `robust`): the imaging
+    weights (`device_imaging_weights`) are formed once from `wgt` and used for
+    the PSF and every invert of the loop; the predict stays unweighted.
+    "natural" uses `wgt` as it is.
+
     Returns a dict: `model`, `residual` (image), `psf`, `peaks` (|peak| at the
     start of each cycle run), `components` (count per cycle) and `stop_reason`
     ("threshold": a cycle started at or below it; "n_major": the cycles ran
@@ -191,6 +199,7 @@ def device_major_cycles(
     _require_gpu()
     npix = int(npix)
     kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
+    wgt, _ = device_imaging_weights(uvw, freq, wgt, npix, npix, pixsize, pixsize, weighting=weighting, robust=robust)
     psf, _ = device_ms2dirty(uvw, freq, None, wgt, npix, npix, pixsize, pixsize, psf=True, normalise=True, **kw)
     residual, _ = device_ms2dirty(uvw, freq, vis, wgt, npix, npix, pixsize, pixsize, normalise=True,
                                   reuse_plan=True, **kw)

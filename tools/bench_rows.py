@@ -21,6 +21,14 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     and the GB/s that implies at 24 B per window pixel, beside
                     the obvious torch loop on the same device (argmax(abs) ->
                     .item() -> sliced sub_) in the same run
+  --mode weights    uniform imaging weights (weighting.py) on bench.py's C3
+                    inputs and geometry: density / statistics / apply and the
+                    one-shot call, best of --repeat; the synchronous
+                    device_ms2dirty step of the same inputs in the same run;
+                    a torch restatement on the same device (cell index,
+                    bincount with weights, gather, divide) and whether its
+                    weights agree; the mean run of equal cells a lane merges
+                    into one atomic add
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -168,9 +176,107 @@ def clean(args):
             "bit_identical_to_torch_loop": bool(torch.equal(res, res_t) and torch.equal(model, model_t))}
 
 
+def weights(args):
+    """ms of the imaging-weights calls, of the invert and of a torch restatement, all on C3's inputs."""
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench  # the flagship workload's own inputs
+
+    from ska_sdp_cip_amd import gridder, weighting
+
+    dev = torch.device("cuda", 0)
+    cfg = bench.CONFIGS[args.config]
+    uvw, freq, vis, wgt, px, _, _ = bench.make_inputs(cfg, 0, 1, dev)
+    npix, nrow, nchan = cfg["npix"], cfg["rows"], cfg["nchan"]
+    nvis = nrow * nchan
+
+    def best(fn):
+        fn()  # warm-up: workspace buffers
+        times = []
+        for _ in range(args.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return min(times) * 1e3
+
+    wd = weighting.WeightDensity(npix, npix, px, px, float(wgt.max()), nvis, dev)
+    out = torch.empty_like(wgt)
+
+    def density():
+        wd.density.zero_()
+        wd.add_ms(uvw, freq, wgt)
+
+    ms_density = best(density)
+    ms_stats = best(lambda: wd.finish("uniform"))
+    ms_apply = best(lambda: wd.apply(uvw, freq, wgt, out=out))
+    info = {}
+
+    def one_shot():
+        info.update(weighting.device_imaging_weights(uvw, freq, wgt, npix, npix, px, px, weighting="uniform",
+                                                     out=out)[1])
+
+    ms_total = best(one_shot)
+    ms_invert = best(lambda: gridder.device_ms2dirty(uvw, freq, vis, wgt, npix, npix, px, px, support=8,
+                                                     do_wstacking=False))
+    hx = hy = npix // 2
+    sx = float(npix) * px
+    keep = {}
+
+    def torch_cells():
+        wi = freq / 299792458.0
+        x = wi[None, :] * (uvw[:, 0] * sx)[:, None]
+        y = wi[None, :] * (uvw[:, 1] * sx)[:, None]
+        sign = torch.where((y < 0) | ((y == 0) & (x < 0)), -1.0, 1.0)
+        fx, fy = torch.floor(sign * x + 0.5), torch.floor(sign * y + 0.5)
+        inside = (fx.abs() <= hx) & (fy <= hy)
+        return torch.where(inside, (fx + hx) * (hy + 1) + fy, -1.0).to(torch.int64), inside
+
+    def torch_run():
+        cell, inside = torch_cells()
+        flat = cell.clamp_(min=0).view(-1)
+        w64 = torch.where(inside, wgt.to(torch.float64), 0.0).view(-1)
+        dens = torch.bincount(flat, weights=w64, minlength=(2 * hx + 1) * (hy + 1))
+        d = dens[flat]
+        keep["w"] = torch.where(d > 0, w64 / d, 0.0).to(torch.float32).view(nrow, nchan)
+
+    ms_torch = best(torch_run)
+    rel = ((keep["w"].double() - out.double()).abs() / out.double().clamp(min=1e-300)).max().item()
+    # the atomics the density kernel issues: a lane merges equal cells of consecutive samples it adds
+    # within its 16 channels (zero weights and outside samples are skipped, not run breaks)
+    cell, inside = torch_cells()
+    added = inside & (wgt > 0)
+    key = torch.where(added, cell, -2)
+    atomics = 0
+    for c0 in range(0, nchan, 16):
+        seg, on = key[:, c0:c0 + 16], added[:, c0:c0 + 16]
+        last = torch.full((nrow,), -2, dtype=torch.int64, device=dev)
+        for k in range(seg.shape[1]):
+            atomics += int((on[:, k] & (seg[:, k] != last)).sum())
+            last = torch.where(on[:, k], seg[:, k], last)
+    n_added = int(added.sum())
+    return {"data": f"bench.py {args.config} inputs and geometry (synthetic uvw tracks, float32 weights, 5% zero)",
+            "rows": nrow, "channels": nchan, "npix": npix, "visibilities": nvis,
+            "metric": "ms per imaging-weights step (uniform, float32 in and out), best of repeats",
+            "value": round(ms_total, 3), "unit": "ms", "repeat": args.repeat,
+            "density_ms": round(ms_density, 3), "stats_ms": round(ms_stats, 3), "apply_ms": round(ms_apply, 3),
+            "one_shot_total_ms": round(ms_total, 3), "ms2dirty_sync_ms": round(ms_invert, 3),
+            "torch_restatement_ms": round(ms_torch, 3),
+            "torch_restatement": "fp64 cell index, torch.bincount(weights=fp64), gather, divide, to float32",
+            "speedup_over_torch": round(ms_torch / ms_total, 2),
+            "torch_max_rel_diff": rel, "torch_weights_agree": bool(rel < 1e-5),
+            "n_added": n_added, "n_outside": info["n_outside"], "n_cells": info["n_cells"],
+            "density_atomics": atomics, "mean_merged_run": round(n_added / max(atomics, 1), 2),
+            "density_GBs_at_4B_per_vis": round(4.0 * nvis / ms_density / 1e6, 1),
+            "apply_GBs_at_8B_per_vis": round(8.0 * nvis / ms_apply / 1e6, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean"), required=True)
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "weights"), required=True)
+    ap.add_argument("--config", default="c3", help="weights: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--npix", type=int, default=2048)
@@ -197,6 +303,9 @@ def main():
 
     if args.mode == "degrid":
         print(json.dumps(degrid(args)), flush=True)
+        return
+    if args.mode == "weights":
+        print(json.dumps(weights(args)), flush=True)
         return
     if args.mode == "clean":
         if args.psf_npix is None:
