@@ -47,51 +47,6 @@ WEIGHTING_MODES = {"natural": CIP_WEIGHT_NATURAL, "uniform": CIP_WEIGHT_UNIFORM,
 CLEAN_STOP_REASONS = {CIP_CLEAN_NITER: "niter", CIP_CLEAN_THRESHOLD: "threshold", CIP_CLEAN_EMPTY: "empty"}
 STOKES_CODES = {"I": 0, "Q": 1, "U": 2, "V": 3}
 
-# every symbol declared in include/cip.h
-EXPORTED_SYMBOLS = (
-    "cip_choose_params",
-    "cip_ms2dirty",
-    "cip_dirty2ms",
-    "cip_hogbom_clean",
-    "cip_weight_grid_init",
-    "cip_weight_density",
-    "cip_weight_stats",
-    "cip_weight_apply",
-    "cip_imaging_weights",
-    "cip_ms2dirty_stokes_i",
-    "cip_grid_plane",
-    "cip_grid_layout",
-    "cip_plane_group",
-    "cip_grid_ms",
-    "cip_grid_ms_stokes_i",
-    "cip_grid_tiles",
-    "cip_grid_tiles_strip",
-    "cip_grid_tiles_strip_mask",
-    "cip_strip_histogram",
-    "cip_strip_split",
-    "cip_ms2dirty_wplanes",
-    "cip_grid_to_dirty",
-    "cip_strip_rows",
-    "cip_strip_rows_masked",
-    "cip_strip_cols",
-    "cip_strip_cols_wplane",
-    "cip_strip_wfinal",
-    "cip_strip_pack_rows",
-    "cip_strip_rows_packed",
-    "cip_strip_unpack_rows",
-    "cip_tile_runs",
-    "cip_stokes_i",
-    "cip_stokes",
-    "cip_facet_rephase",
-    "cip_allreduce_grid",
-    "cip_release_collectives",
-    "cip_last_error",
-    "cip_release_workspace",
-    "cip_profile_enable",
-    "cip_profile_last",
-    "cip_build_info",
-)
-
 PROFILE_PHASES = ("prep", "plan", "scatter", "fft", "correct", "total")
 PROFILE_COUNTS = ("visibilities", "runs", "chunks", "planes", "scatter_launches", "reserved")
 
@@ -177,6 +132,66 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
 _f64 = ctypes.c_double
+_str = ctypes.c_char_p
+_prm = ctypes.POINTER(GridderParams)
+_wgrid = ctypes.POINTER(WeightGrid)
+_pi64 = ctypes.POINTER(ctypes.c_int64)
+_pf64 = ctypes.POINTER(ctypes.c_double)
+_ROWS = [_vp, _i64, _vp, _i64]  # uvw, nrow, freq, nchan
+_VIS_WGT = [_vp, _i32, _vp, _i32]  # vis, vis_dtype, wgt, wgt_dtype
+_IMAGE = [_i64, _i64, _f64, _f64]  # npix_x, npix_y, pixsize_x, pixsize_y
+_SLICES = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32]  # cip_grid_tiles' slices .. wgt_dtype
+_STRIP = [_vp, _prm, _i64, _i64]  # a buffer, params, npix_x, npix_y
+
+# The prototype of every symbol declared in include/cip.h, in its order:
+# name -> (restype, argtypes). A new entry point is one line here.
+PROTOTYPES = {
+    "cip_choose_params": (_i32, [*_IMAGE, _f64, _i32, _i32, _f64, _f64, _prm]),
+    "cip_ms2dirty": (_i32, [*_ROWS, *_VIS_WGT, *_IMAGE, _f64, _i32, _i32, _vp, _vp, _vp, _prm]),
+    "cip_dirty2ms": (_i32, [*_ROWS, _vp, *_IMAGE, _f64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _prm]),
+    "cip_hogbom_clean": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _f64, _f64, _i64, _i64, _vp,
+                                _vp, _vp, _vp, ctypes.POINTER(CleanResult)]),
+    "cip_weight_grid_init": (_i32, [*_IMAGE, _f64, _i64, _wgrid]),
+    "cip_weight_density": (_i32, [*_ROWS, _vp, _i32, _wgrid, _vp, _vp, _pi64]),
+    "cip_weight_stats": (_i32, [_vp, _wgrid, _vp, _pf64]),
+    "cip_weight_apply": (_i32, [*_ROWS, _vp, _i32, _vp, _wgrid, _i32, _f64, _vp, _vp, _i32]),
+    "cip_imaging_weights": (_i32, [*_ROWS, _vp, _i32, *_IMAGE, _i32, _f64, _vp, _vp, _i32,
+                                   ctypes.POINTER(WeightInfo)]),
+    "cip_ms2dirty_wplanes": (_i32, [*_ROWS, *_VIS_WGT, *_IMAGE, _f64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _prm]),
+    "cip_ms2dirty_stokes_i": (_i32, [*_ROWS, _vp, _vp, _vp, *_IMAGE, _f64, _i32, _i32, _vp, _vp, _vp, _prm]),
+    "cip_grid_plane": (_i32, [*_ROWS, *_VIS_WGT, _prm, _f64, _f64, _i64, _i32, _vp, _vp]),
+    "cip_grid_layout": (_i32, [_prm, _i64, _i64]),
+    "cip_plane_group": (_i32, [_prm, _i32]),
+    "cip_grid_ms": (_i32, [*_ROWS, *_VIS_WGT, _prm, _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cip_grid_ms_stokes_i": (_i32, [*_ROWS, _vp, _vp, _vp, _prm, _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cip_grid_tiles": (_i32, [*_SLICES, _prm, _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cip_grid_tiles_strip": (_i32, [*_SLICES, _prm, _f64, _f64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cip_grid_tiles_strip_mask": (_i32, [*_SLICES, _prm, _f64, _f64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp,
+                                         _vp]),
+    "cip_strip_histogram": (_i32, [*_ROWS, _prm, _f64, _f64, _vp, _vp]),
+    "cip_strip_split": (_i32, [*_ROWS, *_VIS_WGT, _prm, _f64, _i64, _i64, _vp, _pi64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cip_grid_to_dirty": (_i32, [*_STRIP, _f64, _f64, _vp, _vp]),
+    "cip_strip_rows": (_i32, [*_STRIP, _i64, _i64, _vp, _vp]),
+    "cip_strip_cols": (_i32, [*_STRIP, _i64, _i64, _vp, _vp, _vp]),
+    "cip_strip_rows_masked": (_i32, [*_STRIP, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "cip_strip_rows_packed": (_i32, [*_STRIP, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "cip_strip_pack_rows": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "cip_strip_unpack_rows": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "cip_strip_cols_wplane": (_i32, [*_STRIP, _f64, _f64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "cip_strip_wfinal": (_i32, [*_STRIP, _f64, _f64, _i64, _i64, _vp, _vp]),
+    "cip_tile_runs": (_i32, [*_ROWS, _pf64, _i64, _vp, _pi64, _vp, _vp, _vp, _vp]),
+    "cip_stokes_i": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cip_stokes": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "cip_facet_rephase": (_i32, [*_ROWS, _vp, _i32, _f64, _f64, _vp, _vp, _vp]),
+    "cip_allreduce_grid": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp]),
+    "cip_release_collectives": (_i32, []),
+    "cip_last_error": (_str, []),
+    "cip_release_workspace": (_i32, []),
+    "cip_profile_enable": (_i32, [_i32]),
+    "cip_profile_last": (_i32, [_vp, _vp]),
+    "cip_build_info": (_str, []),
+}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 
 def lib() -> ctypes.CDLL:
@@ -192,75 +207,9 @@ def lib() -> ctypes.CDLL:
             "(make -C ska-sdp-continuum-imaging-pipeline_amd/csrc)"
         )
     so = ctypes.CDLL(str(path))
-    so.cip_choose_params.argtypes = [_i64, _i64, _f64, _f64, _f64, _i32, _i32, _f64, _f64,
-                                     ctypes.POINTER(GridderParams)]
-    so.cip_ms2dirty.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _f64, _f64,
-                                _f64, _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
-    so.cip_dirty2ms.argtypes = [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _f64, _f64, _f64, _i32, _i32, _vp, _i32,
-                                _vp, _vp, _i32, ctypes.POINTER(GridderParams)]
-    so.cip_hogbom_clean.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _f64, _f64, _i64, _i64, _vp,
-                                    _vp, _vp, _vp, ctypes.POINTER(CleanResult)]
-    so.cip_weight_grid_init.argtypes = [_i64, _i64, _f64, _f64, _f64, _i64, ctypes.POINTER(WeightGrid)]
-    so.cip_weight_density.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, ctypes.POINTER(WeightGrid), _vp, _vp,
-                                      ctypes.POINTER(ctypes.c_int64)]
-    so.cip_weight_stats.argtypes = [_vp, ctypes.POINTER(WeightGrid), _vp, ctypes.POINTER(ctypes.c_double)]
-    so.cip_weight_apply.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, ctypes.POINTER(WeightGrid), _i32, _f64,
-                                    _vp, _vp, _i32]
-    so.cip_imaging_weights.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _i64, _f64, _f64, _i32, _f64, _vp,
-                                       _vp, _i32, ctypes.POINTER(WeightInfo)]
-    so.cip_ms2dirty_wplanes.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _f64, _f64,
-                                        _f64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
-    so.cip_ms2dirty_stokes_i.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _f64, _f64,
-                                         _f64, _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(GridderParams)]
-    so.cip_grid_plane.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32,
-                                  ctypes.POINTER(GridderParams), _f64, _f64, _i64, _i32, _vp, _vp]
-    so.cip_grid_layout.argtypes = [ctypes.POINTER(GridderParams), _i64, _i64]
-    so.cip_plane_group.argtypes = [ctypes.POINTER(GridderParams), _i32]
-    so.cip_grid_ms.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, ctypes.POINTER(GridderParams),
-                               _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]
-    so.cip_grid_ms_stokes_i.argtypes = [_vp, _i64, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(GridderParams),
-                                        _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]
-    so.cip_grid_tiles.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32,
-                                  ctypes.POINTER(GridderParams), _f64, _f64, _i64, _i64, _i32, _vp, _vp, _vp]
-    so.cip_grid_tiles_strip.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32,
-                                        ctypes.POINTER(GridderParams), _f64, _f64, _i64, _i64, _i64, _i64, _i32,
-                                        _vp, _vp, _vp]
-    so.cip_grid_tiles_strip_mask.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32,
-                                             ctypes.POINTER(GridderParams), _f64, _f64, _i64, _i64, _i64, _i64, _i32,
-                                             _vp, _vp, _vp, _vp]
-    so.cip_strip_histogram.argtypes = [_vp, _i64, _vp, _i64, ctypes.POINTER(GridderParams), _f64, _f64, _vp, _vp]
-    so.cip_strip_split.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, ctypes.POINTER(GridderParams), _f64,
-                                   _i64, _i64, _vp, ctypes.POINTER(ctypes.c_int64), _vp, _vp, _vp, _vp, _vp, _vp]
-    so.cip_grid_to_dirty.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _f64, _f64, _vp, _vp]
-    so.cip_strip_rows.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _i64, _i64, _vp, _vp]
-    so.cip_strip_cols.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _i64, _i64, _vp, _vp, _vp]
-    so.cip_strip_rows_masked.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _i64, _i64, _i64, _vp,
-                                         _vp, _vp]
-    so.cip_strip_cols_wplane.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _f64, _f64, _i64, _i64,
-                                         _i64, _i32, _vp, _vp]
-    so.cip_strip_wfinal.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _f64, _f64, _i64, _i64, _vp,
-                                    _vp]
-    so.cip_strip_pack_rows.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]
-    so.cip_strip_rows_packed.argtypes = [_vp, ctypes.POINTER(GridderParams), _i64, _i64, _i64, _i64, _i64, _vp,
-                                         _vp, _i64, _vp, _vp]
-    so.cip_strip_unpack_rows.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]
-    so.cip_tile_runs.argtypes = [_vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_double), _i64, _vp,
-                                 ctypes.POINTER(ctypes.c_int64), _vp, _vp, _vp, _vp]
-    so.cip_stokes_i.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
-    so.cip_stokes.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
-    so.cip_allreduce_grid.argtypes = [_vp, _vp, _i32, _i64, _i32, _vp]
-    so.cip_facet_rephase.argtypes = [_vp, _i64, _vp, _i64, _vp, _i32, _f64, _f64, _vp, _vp, _vp]
-    so.cip_profile_enable.argtypes = [_i32]
-    so.cip_profile_last.argtypes = [_vp, _vp]
-    so.cip_last_error.restype = ctypes.c_char_p
-    so.cip_build_info.restype = ctypes.c_char_p
-    for name in ("cip_choose_params", "cip_ms2dirty", "cip_dirty2ms", "cip_hogbom_clean", "cip_ms2dirty_stokes_i", "cip_grid_plane", "cip_grid_layout", "cip_plane_group", "cip_grid_ms", "cip_grid_ms_stokes_i",
-                 "cip_grid_tiles", "cip_grid_tiles_strip", "cip_grid_tiles_strip_mask", "cip_strip_histogram",
-                 "cip_strip_split", "cip_ms2dirty_wplanes", "cip_grid_to_dirty", "cip_strip_rows", "cip_strip_rows_masked", "cip_strip_cols", "cip_strip_cols_wplane", "cip_strip_wfinal", "cip_strip_pack_rows", "cip_strip_unpack_rows", "cip_strip_rows_packed", "cip_tile_runs",
-                 "cip_stokes_i", "cip_stokes", "cip_facet_rephase", "cip_allreduce_grid", "cip_release_collectives",
-                 "cip_release_workspace", "cip_profile_enable", "cip_profile_last", "cip_weight_grid_init",
-                 "cip_weight_density", "cip_weight_stats", "cip_weight_apply", "cip_imaging_weights"):
-        getattr(so, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(so, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = so
     return so
 

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .gridder import _codes, _require_gpu
+from ._call import STREAM, call, check_array, check_tensor, require_gpu, target_device, vis_arg, wgt_arg
 
 try:
     import torch
@@ -78,7 +78,7 @@ class GridAccumulator:
                  epsilon: float = 1e-4, support: Optional[int] = None, do_wstacking: bool = False,
                  w_range: tuple[float, float] = (0.0, 0.0), device=None,
                  single_precision_accumulation: bool = False):
-        _require_gpu()
+        require_gpu()
         self.npix_x, self.npix_y = int(npix_x), int(npix_y)
         self.pixsize_x, self.pixsize_y = float(pixsize_x), float(pixsize_y)
         wmin, wmax = w_range
@@ -86,7 +86,7 @@ class GridAccumulator:
             wmin = wmax = 0.0
         self.params = _lib.choose_params(npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support or 0,
                                          do_wstacking, wmin, wmax)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = target_device(device)
         p = self.params
         self.planes = torch.zeros((p.nplanes, p.nu * p.nv * 2), dtype=torch.float64, device=self.device)
         self.sum_weights = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -99,25 +99,19 @@ class GridAccumulator:
         if self._done:
             raise RuntimeError("dirty() consumed the grid planes; make a new GridAccumulator")
         for t in tensors:
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.device != self.device):
-                raise ValueError("chunks must be contiguous tensors on the accumulator's device")
+            if t is not None:
+                check_tensor(t, self.device, "chunks")
 
     def add_ms(self, uvw, freq, vis, wgt=None) -> None:
         """Add MS rows: uvw (nrow, 3) f64, freq (nchan) f64, vis (nrow, nchan)
         complex64/128, wgt (nrow, nchan) f32/f64 or None."""
-        vis_codes, wgt_codes = _codes()
         self._check(uvw, freq, vis, wgt)
         nrow, nchan = uvw.shape[0], freq.shape[0]
         if tuple(vis.shape) != (nrow, nchan) or (wgt is not None and tuple(wgt.shape) != (nrow, nchan)):
             raise ValueError("vis / wgt must have shape (nrow, nchan)")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().cip_grid_ms(
-                uvw.data_ptr(), nrow, freq.data_ptr(), nchan, vis.data_ptr(), vis_codes[vis.dtype],
-                wgt.data_ptr() if wgt is not None else None,
-                wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
-                self.params, self.pixsize_x, self.pixsize_y, self.npix_x, self.npix_y, self.flags, stream,
-                self.planes.data_ptr(), self.sum_weights.data_ptr()))
+        call(self.device, "cip_grid_ms", uvw, nrow, freq, nchan, *vis_arg(vis), *wgt_arg(wgt), self.params,
+             self.pixsize_x, self.pixsize_y, self.npix_x, self.npix_y, self.flags, STREAM, self.planes,
+             self.sum_weights)
         self.num_visibilities += nrow * nchan
 
     def add_ms_stokes_i(self, uvw, freq, vis4, flags4, wgt4) -> None:
@@ -133,20 +127,15 @@ class GridAccumulator:
             raise ValueError(f"vis4 complex64, wgt4 float32 and flags4 must have shape {shape}")
         if flags4 is not None and flags4.dtype == torch.bool:
             flags4 = flags4.view(torch.uint8)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().cip_grid_ms_stokes_i(
-                uvw.data_ptr(), nrow, freq.data_ptr(), nchan, vis4.data_ptr(),
-                None if flags4 is None else flags4.data_ptr(), wgt4.data_ptr(), self.params, self.pixsize_x,
-                self.pixsize_y, self.npix_x, self.npix_y, self.flags, stream, self.planes.data_ptr(),
-                self.sum_weights.data_ptr()))
+        call(self.device, "cip_grid_ms_stokes_i", uvw, nrow, freq, nchan, vis4, flags4, wgt4, self.params,
+             self.pixsize_x, self.pixsize_y, self.npix_x, self.npix_y, self.flags, STREAM, self.planes,
+             self.sum_weights)
         self.num_visibilities += nrow * nchan
 
     def add_tile(self, slice_uvw, chan_start, chan_stop, freq, vis, wgt=None) -> None:
         """Add one tile chunk (Tile layout): slice_uvw (ns, 3) f64, chan_start /
         chan_stop (ns) int32, freq (nchan) f64, vis (nvis) complex, wgt (nvis)
         f32/f64 or None (unit weights, as the reference's tiles carry none)."""
-        vis_codes, wgt_codes = _codes()
         self._check(slice_uvw, chan_start, chan_stop, freq, vis, wgt)
         if chan_start.dtype != torch.int32 or chan_stop.dtype != torch.int32:
             raise ValueError("channel ranges must be int32")
@@ -154,15 +143,10 @@ class GridAccumulator:
         nvis = vis.shape[0]
         if wgt is not None and tuple(wgt.shape) != (nvis,):
             raise ValueError("wgt must have the shape of vis")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().cip_grid_tiles(
-                slice_uvw.data_ptr(), chan_start.data_ptr(), chan_stop.data_ptr(), ns, freq.data_ptr(),
-                freq.shape[0], vis.data_ptr(), nvis, vis_codes[vis.dtype],
-                wgt.data_ptr() if wgt is not None else None,
-                wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
-                self.params, self.pixsize_x, self.pixsize_y, self.npix_x, self.npix_y, self.flags, stream,
-                self.planes.data_ptr(), self.sum_weights.data_ptr()))
+        vis_ptr, vis_code = vis_arg(vis)
+        call(self.device, "cip_grid_tiles", slice_uvw, chan_start, chan_stop, ns, freq, freq.shape[0], vis_ptr, nvis,
+             vis_code, *wgt_arg(wgt), self.params, self.pixsize_x, self.pixsize_y, self.npix_x, self.npix_y,
+             self.flags, STREAM, self.planes, self.sum_weights)
         self.num_visibilities += nvis
 
     def dirty(self, out=None):
@@ -171,15 +155,10 @@ class GridAccumulator:
         self._check()
         if out is None:
             out = torch.empty((self.npix_x, self.npix_y), dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or tuple(out.shape) != (self.npix_x, self.npix_y) or \
-                not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"out must be a contiguous float64 ({self.npix_x}, {self.npix_y}) tensor on "
-                             f"{self.device}")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().cip_grid_to_dirty(self.planes.data_ptr(), self.params, self.npix_x,
-                                                    self.npix_y, self.pixsize_x, self.pixsize_y, stream,
-                                                    out.data_ptr()))
+        else:
+            check_array(out, (torch.float64,), (self.npix_x, self.npix_y), self.device, "out")
+        call(self.device, "cip_grid_to_dirty", self.planes, self.params, self.npix_x, self.npix_y, self.pixsize_x,
+             self.pixsize_y, STREAM, out)
         self._done = True
         return out, self.sum_weights
 

@@ -22,7 +22,8 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from .gridder import _require_gpu, device_facet_rephase, device_ms2dirty, device_stokes
+from ._call import require_gpu
+from .gridder import device_facet_rephase, device_ms2dirty, device_stokes
 from .invert import EPSILON, pixel_size_lm
 
 try:
@@ -68,7 +69,7 @@ def continuum_invert(
     `single_precision_accumulation`: the packed single-precision class (ducc0's
     float class of the reference's complex64 call) instead of fp64.
     """
-    _require_gpu()
+    require_gpu()
     pix = pixel_size_lm(pixel_size_asec)
     facets = [(0.0, 0.0)] if facets is None else list(facets)
     stokes = list(stokes)
@@ -103,7 +104,7 @@ def continuum_invert(
 def continuum_invert_measurement_set(ms_reader, facet_pixels: int, pixel_size_asec: float, **kwargs) -> dict:
     """`continuum_invert` of a measurement set reader's columns (moved to the
     current device once); images returned as float32 numpy arrays."""
-    _require_gpu()
+    require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
 
     def t(a, dt):

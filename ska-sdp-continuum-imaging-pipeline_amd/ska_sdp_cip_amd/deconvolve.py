@@ -17,7 +17,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .gridder import _check_device_tensor, _require_gpu, _to_device, device_ms2dirty
+from ._call import STREAM, call, check_array, require_gpu, target_device, to_device
+from .gridder import device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .predict import device_residual
 from .weighting import device_imaging_weights
@@ -59,25 +60,17 @@ def device_hogbom_clean(
     readbacks of the device state (0: library default); the result does not
     depend on it.
     """
-    _require_gpu()
-    if residual.dim() != 2 or residual.dtype != torch.float64:
-        raise ValueError(f"residual must be a float64 (nx, ny) image, got {residual.dtype} {tuple(residual.shape)}")
-    if psf.dim() != 2 or psf.dtype != torch.float64:
-        raise ValueError(f"psf must be a float64 (px, py) image, got {psf.dtype} {tuple(psf.shape)}")
-    dev = residual.device
-    _check_device_tensor(residual, dev, "residual")
-    _check_device_tensor(psf, dev, "psf")
-    shape = tuple(residual.shape)
+    require_gpu()
+    dev, shape = residual.device, tuple(residual.shape)
+    for name, img in (("residual", residual), ("psf", psf)):
+        if img.dim() != 2:
+            raise ValueError(f"{name} must be a float64 2-D image, got {img.dtype} {tuple(img.shape)}")
+        check_array(img, (torch.float64,), None, dev, name)
     if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        if mask.dtype != torch.uint8 or tuple(mask.shape) != shape:
-            raise ValueError(f"mask must be uint8 / bool of shape {shape}")
-        _check_device_tensor(mask, dev, "mask")
+        check_array(mask, (torch.uint8, torch.bool), shape, dev, "mask")
+        mask = mask.view(torch.uint8)
     if model is not None:
-        if model.dtype != torch.float64 or tuple(model.shape) != shape:
-            raise ValueError(f"model must be float64 of shape {shape}")
-        _check_device_tensor(model, dev, "model")
+        check_array(model, (torch.float64,), shape, dev, "model")
     cx, cy = (-1, -1) if psf_centre is None else (int(psf_centre[0]), int(psf_centre[1]))
     if psf_centre is not None and (cx < 0 or cy < 0):
         raise ValueError("psf_centre must lie inside the PSF")
@@ -90,14 +83,8 @@ def device_hogbom_clean(
         comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
         comp_flux = torch.empty(max(niter, 1), dtype=torch.float64, device=dev)
     result = _lib.CleanResult()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().cip_hogbom_clean(
-            res.data_ptr(), shape[0], shape[1], psf.data_ptr(), int(psf.shape[0]), int(psf.shape[1]), cx, cy,
-            None if mask is None else mask.data_ptr(), float(gain), float(threshold), niter, int(batch), stream,
-            model.data_ptr(), None if comp_index is None else comp_index.data_ptr(),
-            None if comp_flux is None else comp_flux.data_ptr(), ctypes.byref(result))
-    _lib.check(rc)
+    call(dev, "cip_hogbom_clean", res, shape[0], shape[1], psf, int(psf.shape[0]), int(psf.shape[1]), cx, cy, mask,
+         float(gain), float(threshold), niter, int(batch), STREAM, model, comp_index, comp_flux, ctypes.byref(result))
     info = {
         "niter_done": int(result.niter_done),
         "stop_reason": int(result.stop_reason),
@@ -130,17 +117,17 @@ def hogbom_clean(
     torch in -> torch out (on the GPU). The inputs are never modified. Returns
     (model, residual, info) as `device_hogbom_clean`.
     """
-    _require_gpu()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    require_gpu()
+    dev = target_device(device)
     numpy_in = isinstance(residual, np.ndarray)
     with torch.cuda.device(dev):
-        res_d = _to_device(residual, torch.float64, dev)
-        psf_d = _to_device(psf, torch.float64, dev)
+        res_d = to_device(residual, torch.float64, dev)
+        psf_d = to_device(psf, torch.float64, dev)
         mask_d = None
         if mask is not None:
             m = np.asarray(mask) if not torch.is_tensor(mask) else mask
-            mask_d = _to_device(m != 0, torch.bool, dev)
-        model_d = None if model is None else _to_device(model, torch.float64, dev).clone()
+            mask_d = to_device(m != 0, torch.bool, dev)
+        model_d = None if model is None else to_device(model, torch.float64, dev).clone()
         model_d, res_d, info = device_hogbom_clean(
             res_d, psf_d, gain=gain, threshold=threshold, niter=niter, mask=mask_d, model=model_d,
             psf_centre=psf_centre, inplace=False, return_components=return_components, batch=batch)
@@ -196,7 +183,7 @@ def device_major_cycles(
     ("threshold": a cycle started at or below it; "n_major": the cycles ran
     out; "empty": the mask allows no pixel).
     """
-    _require_gpu()
+    require_gpu()
     npix = int(npix)
     kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
     wgt, _ = device_imaging_weights(uvw, freq, wgt, npix, npix, pixsize, pixsize, weighting=weighting, robust=robust)

@@ -25,36 +25,13 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._call import (STREAM, VIS_DTYPES, WGT_DTYPES, call, check_array, check_rows, require_gpu, target_device,
+                    to_device, vis_arg, wgt_arg)
 
 try:  # torch is plumbing (device memory, streams); import lazily-safe
     import torch
 except ModuleNotFoundError:  # pragma: no cover - torch is in the image
     torch = None
-
-
-def _require_gpu():
-    if torch is None or not torch.cuda.is_available():
-        raise RuntimeError(
-            "ska_sdp_cip_amd.ms2dirty needs a ROCm GPU (MI355X); no CPU fallback"
-        )
-
-
-def _to_device(x, dtype, device):
-    if isinstance(x, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(x))
-        return t.to(device=device, dtype=dtype, non_blocking=False)
-    return x.to(device=device, dtype=dtype).contiguous()
-
-
-_VIS_CODES = {}
-_WGT_CODES = {}
-
-
-def _codes():
-    if not _VIS_CODES:
-        _VIS_CODES.update({torch.complex64: _lib.CIP_C64, torch.complex128: _lib.CIP_C128})
-        _WGT_CODES.update({torch.float32: _lib.CIP_F32, torch.float64: _lib.CIP_F64})
-    return _VIS_CODES, _WGT_CODES
 
 
 def device_ms2dirty(
@@ -117,88 +94,55 @@ def device_ms2dirty(
     """
     if planes is not None and not do_wstacking:
         raise ValueError("planes=(begin, end) needs do_wstacking=True")
+    if psf:
+        vis = None  # never read
+    elif vis is None:
+        raise ValueError("vis dtype must be complex64/complex128, got None")
+    vis_args, wgt_args = vis_arg(vis), wgt_arg(wgt)
+    nrow, nchan = check_rows(uvw, freq, "device_ms2dirty inputs")
+    if vis is not None:
+        check_array(vis, VIS_DTYPES, (nrow, nchan), uvw.device, "ms")
+    if wgt is not None:
+        check_array(wgt, WGT_DTYPES, (nrow, nchan), uvw.device, "wgt")
+    out = _invert_outputs(out, sum_weights, npix_x, npix_y, uvw.device, synchronize, resident_inputs, reuse_plan)
+    params = _lib.GridderParams()
+    call(uvw.device, "cip_ms2dirty" if planes is None else "cip_ms2dirty_wplanes",
+         uvw, nrow, freq, nchan, *vis_args, *wgt_args, int(npix_x), int(npix_y), float(pixsize_x),
+         float(pixsize_y), float(epsilon), int(support or 0),
+         _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
+                       reuse_plan),
+         *(() if planes is None else (int(planes[0]), int(planes[1]))), STREAM, out, sum_weights, params)
+    return out, params
+
+
+def _invert_outputs(out, sum_weights, npix_x, npix_y, device, synchronize, resident_inputs, reuse_plan):
+    """The flag guards and the `out` / `sum_weights` checks of the device_ms2dirty* calls; returns `out`
+    (allocated when None)."""
     if resident_inputs and synchronize:
         raise ValueError("resident_inputs=True needs synchronize=False")
     if reuse_plan and resident_inputs:
         raise ValueError("reuse_plan=True cannot be combined with resident_inputs=True")
-    vis_codes, wgt_codes = _codes()
-    if psf:
-        vis = None  # never read
-    elif vis is None or vis.dtype not in vis_codes:
-        raise ValueError(f"vis dtype must be complex64/complex128, got {getattr(vis, 'dtype', None)}")
-    if wgt is not None and wgt.dtype not in wgt_codes:
-        raise ValueError(f"wgt dtype must be float32/float64, got {wgt.dtype}")
-    nrow = uvw.shape[0]
-    nchan = freq.shape[0]
-    if tuple(uvw.shape) != (nrow, 3):
-        raise ValueError("uvw must have shape (nrow, 3)")
-    if vis is not None and tuple(vis.shape) != (nrow, nchan):
-        raise ValueError(f"ms must have shape ({nrow}, {nchan}), got {tuple(vis.shape)}")
-    if wgt is not None and tuple(wgt.shape) != (nrow, nchan):
-        raise ValueError("wgt must have the shape of ms")
-    if uvw.dtype != torch.float64 or freq.dtype != torch.float64:
-        raise ValueError("uvw and freq must be float64")
-    for t in (uvw, freq) + ((vis,) if vis is not None else ()) + ((wgt,) if wgt is not None else ()):
-        _check_device_tensor(t, uvw.device, "device_ms2dirty inputs")
     if out is None:
-        out = torch.empty((npix_x, npix_y), dtype=torch.float64, device=uvw.device)
-    else:
-        # the library writes npix_x * npix_y doubles through the raw pointer
-        if out.dtype != torch.float64 or tuple(out.shape) != (int(npix_x), int(npix_y)):
-            raise ValueError(f"out must be float64 of shape ({npix_x}, {npix_y}), "
-                             f"got {out.dtype} {tuple(out.shape)}")
-        _check_device_tensor(out, uvw.device, "out")
+        out = torch.empty((npix_x, npix_y), dtype=torch.float64, device=device)
+    else:  # the library writes npix_x * npix_y doubles through the raw pointer
+        check_array(out, (torch.float64,), (int(npix_x), int(npix_y)), device, "out")
     if sum_weights is not None:
-        if sum_weights.dtype != torch.float64 or sum_weights.numel() != 1:
+        if sum_weights.numel() != 1:
             raise ValueError("sum_weights must be a float64 tensor of one element")
-        _check_device_tensor(sum_weights, uvw.device, "sum_weights")
-    params = _lib.GridderParams()
-    with torch.cuda.device(uvw.device):
-        stream = torch.cuda.current_stream(uvw.device).cuda_stream
-        rc = _ms2dirty_call(uvw, freq, vis, wgt, vis_codes, wgt_codes, npix_x, npix_y, pixsize_x, pixsize_y,
-                            epsilon, support, do_wstacking, single_precision_accumulation, psf, normalise,
-                            stream, out, sum_weights, params, synchronize, resident_inputs, reuse_plan, planes)
-    _lib.check(rc)
-    return out, params
+        check_array(sum_weights, (torch.float64,), None, device, "sum_weights")
+    return out
 
 
-def _check_device_tensor(t, device, what):
-    """Contiguous, on a GPU, and on `device` (the library works on the current
-    device, which the callers set to `device`)."""
-    if not t.is_cuda or not t.is_contiguous():
-        raise ValueError(f"{what}: need contiguous device tensors")
-    if t.device != device:
-        raise ValueError(f"{what}: tensor on {t.device}, expected {device}")
-
-
-def _invert_flags(do_wstacking, single, psf, normalise, synchronize, resident_inputs, reuse_plan):
-    """The CIP_* flag word of a cip_ms2dirty* call."""
+def _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
+                  reuse_plan):
+    """The CIP_* flag word of a cip_ms2dirty* call, from device_ms2dirty's keywords."""
     return ((_lib.CIP_WSTACKING if do_wstacking else 0)
-            | (_lib.CIP_ACC_SINGLE if single else 0)
+            | (_lib.CIP_ACC_SINGLE if single_precision_accumulation else 0)
             | (_lib.CIP_PSF if psf else 0)
             | (_lib.CIP_NORMALISE if normalise else 0)
             | (0 if synchronize else _lib.CIP_ASYNC)
             | (_lib.CIP_PIPELINE if resident_inputs else 0)
             | (_lib.CIP_REUSE_PLAN if reuse_plan else 0))
-
-
-def _ms2dirty_call(uvw, freq, vis, wgt, vis_codes, wgt_codes, npix_x, npix_y, pixsize_x, pixsize_y, epsilon,
-                   support, do_wstacking, single_precision_accumulation, psf, normalise, stream, out,
-                   sum_weights, params, synchronize=True, resident_inputs=False, reuse_plan=False, planes=None):
-    nrow = uvw.shape[0]
-    nchan = freq.shape[0]
-    head = (uvw.data_ptr(), nrow, freq.data_ptr(), nchan, None if vis is None else vis.data_ptr(),
-            _lib.CIP_C64 if vis is None else vis_codes[vis.dtype],
-            wgt.data_ptr() if wgt is not None else None,
-            wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
-            int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y), float(epsilon),
-            int(support or 0),
-            _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
-                          reuse_plan))
-    tail = (stream, out.data_ptr(), sum_weights.data_ptr() if sum_weights is not None else None, params)
-    if planes is not None:
-        return _lib.lib().cip_ms2dirty_wplanes(*head, int(planes[0]), int(planes[1]), *tail)
-    return _lib.lib().cip_ms2dirty(*head, *tail)
 
 
 def device_ms2dirty_stokes_i(
@@ -233,50 +177,27 @@ def device_ms2dirty_stokes_i(
     columns; the image is bit-identical to device_stokes_i + device_ms2dirty.
     Keyword arguments as device_ms2dirty.
     """
-    if resident_inputs and synchronize:
-        raise ValueError("resident_inputs=True needs synchronize=False")
-    if reuse_plan and resident_inputs:
-        raise ValueError("reuse_plan=True cannot be combined with resident_inputs=True")
-    nrow, nchan = uvw.shape[0], freq.shape[0]
-    shape = (nrow, nchan, 4)
+    nrow, nchan = check_rows(uvw, freq, "device_ms2dirty_stokes_i inputs")
+    dev, shape = uvw.device, (nrow, nchan, 4)
     if psf:
         vis4 = None
-    elif vis4 is None or vis4.dtype != torch.complex64 or tuple(vis4.shape) != shape:
+    elif vis4 is None:
         raise ValueError(f"vis4 must be complex64 of shape {shape}")
-    if wgt4 is None or wgt4.dtype != torch.float32 or tuple(wgt4.shape) != shape:
-        raise ValueError(f"wgt4 must be float32 of shape {shape}")
-    if flags4 is not None:
-        if tuple(flags4.shape) != shape:
-            raise ValueError(f"flags4 must have shape {shape}")
-        if flags4.dtype == torch.bool:
-            flags4 = flags4.view(torch.uint8)
-        elif flags4.dtype != torch.uint8:
-            raise ValueError("flags4 must be bool or uint8")
-    if tuple(uvw.shape) != (nrow, 3) or uvw.dtype != torch.float64 or freq.dtype != torch.float64:
-        raise ValueError("uvw must be float64 (nrow, 3) and freq float64")
-    for t in (uvw, freq, wgt4) + tuple(x for x in (vis4, flags4) if x is not None):
-        _check_device_tensor(t, uvw.device, "device_ms2dirty_stokes_i inputs")
-    if out is None:
-        out = torch.empty((npix_x, npix_y), dtype=torch.float64, device=uvw.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (int(npix_x), int(npix_y)):
-        raise ValueError(f"out must be float64 of shape ({npix_x}, {npix_y})")
     else:
-        _check_device_tensor(out, uvw.device, "out")
-    if sum_weights is not None:
-        if sum_weights.dtype != torch.float64 or sum_weights.numel() != 1:
-            raise ValueError("sum_weights must be a float64 tensor of one element")
-        _check_device_tensor(sum_weights, uvw.device, "sum_weights")
+        check_array(vis4, (torch.complex64,), shape, dev, "vis4")
+    if wgt4 is None:
+        raise ValueError(f"wgt4 must be float32 of shape {shape}")
+    check_array(wgt4, (torch.float32,), shape, dev, "wgt4")
+    if flags4 is not None:
+        check_array(flags4, (torch.bool, torch.uint8), shape, dev, "flags4")
+        flags4 = flags4.view(torch.uint8)
+    out = _invert_outputs(out, sum_weights, npix_x, npix_y, dev, synchronize, resident_inputs, reuse_plan)
     params = _lib.GridderParams()
-    with torch.cuda.device(uvw.device):
-        stream = torch.cuda.current_stream(uvw.device).cuda_stream
-        rc = _lib.lib().cip_ms2dirty_stokes_i(
-            uvw.data_ptr(), nrow, freq.data_ptr(), nchan, None if vis4 is None else vis4.data_ptr(),
-            None if flags4 is None else flags4.data_ptr(), wgt4.data_ptr(), int(npix_x), int(npix_y),
-            float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
-            _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
-                          reuse_plan),
-            stream, out.data_ptr(), sum_weights.data_ptr() if sum_weights is not None else None, params)
-    _lib.check(rc)
+    call(dev, "cip_ms2dirty_stokes_i", uvw, nrow, freq, nchan, vis4, flags4, wgt4, int(npix_x), int(npix_y),
+         float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
+         _invert_flags(do_wstacking, single_precision_accumulation, psf, normalise, synchronize, resident_inputs,
+                       reuse_plan),
+         STREAM, out, sum_weights, params)
     return out, params
 
 
@@ -287,26 +208,24 @@ def device_stokes(vis4: "torch.Tensor", flags4: "torch.Tensor", wgt4: "torch.Ten
     bit-exact): -> (visibilities complex64 (nrow, nchan), effective weights
     float32 (nrow, nchan)).
     """
-    _require_gpu()
+    require_gpu()
     if stokes not in _lib.STOKES_CODES:
         raise ValueError(f"stokes must be one of I, Q, U, V, got {stokes!r}")
-    if vis4.dtype != torch.complex64 or wgt4.dtype != torch.float32:
-        raise ValueError("vis4 must be complex64 and wgt4 float32")
-    if vis4.dim() != 3 or vis4.shape[-1] != 4 or tuple(flags4.shape) != tuple(vis4.shape) or \
-            tuple(wgt4.shape) != tuple(vis4.shape):
+    return _stokes("cip_stokes", vis4, flags4, wgt4, _lib.STOKES_CODES[stokes])
+
+
+def _stokes(name, vis4, flags4, wgt4, *code):
+    """device_stokes / device_stokes_i: the checks, the outputs and the call (`code`: cip_stokes' parameter)."""
+    if vis4.dim() != 3 or vis4.shape[-1] != 4:
         raise ValueError("vis4, flags4, wgt4 must all have shape (nrow, nchan, 4)")
+    dev, shape = vis4.device, tuple(vis4.shape)
     fl = flags4.to(torch.uint8) if flags4.dtype != torch.uint8 else flags4
-    for t in (vis4, fl, wgt4):
-        if not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("device_stokes needs contiguous device tensors")
-    nrow, nchan = vis4.shape[0], vis4.shape[1]
-    vis_s = torch.empty((nrow, nchan), dtype=torch.complex64, device=vis4.device)
-    eff = torch.empty((nrow, nchan), dtype=torch.float32, device=vis4.device)
-    with torch.cuda.device(vis4.device):
-        stream = torch.cuda.current_stream(vis4.device).cuda_stream
-        _lib.check(_lib.lib().cip_stokes(vis4.data_ptr(), fl.data_ptr(), wgt4.data_ptr(), nrow * nchan,
-                                         _lib.STOKES_CODES[stokes], stream, vis_s.data_ptr(), None, None,
-                                         eff.data_ptr()))
+    check_array(vis4, (torch.complex64,), shape, dev, "vis4")
+    check_array(fl, (torch.uint8,), shape, dev, "flags4")
+    check_array(wgt4, (torch.float32,), shape, dev, "wgt4")
+    vis_s = torch.empty(shape[:2], dtype=torch.complex64, device=dev)
+    eff = torch.empty(shape[:2], dtype=torch.float32, device=dev)
+    call(dev, name, vis4, fl, wgt4, shape[0] * shape[1], *code, STREAM, vis_s, None, None, eff)
     return vis_s, eff
 
 
@@ -319,22 +238,14 @@ def device_facet_rephase(uvw: "torch.Tensor", freq: "torch.Tensor", vis: Optiona
     tangent plane centred on (l0, m0). Returns (uvw_f, vis_f); vis may be None
     (uvw only, for a facet PSF).
     """
-    _require_gpu()
-    vis_codes, _ = _codes()
-    nrow, nchan = uvw.shape[0], freq.shape[0]
-    if vis is not None and (vis.dtype not in vis_codes or tuple(vis.shape) != (nrow, nchan)):
-        raise ValueError("vis must be complex64/complex128 of shape (nrow, nchan)")
-    for t in (uvw, freq) + ((vis,) if vis is not None else ()):
-        if not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("device_facet_rephase needs contiguous device tensors")
+    require_gpu()
+    nrow, nchan = check_rows(uvw, freq, "device_facet_rephase inputs")
+    if vis is not None:
+        check_array(vis, VIS_DTYPES, (nrow, nchan), uvw.device, "vis")
     uvw_f = torch.empty_like(uvw)
     vis_f = torch.empty_like(vis) if vis is not None else None
-    with torch.cuda.device(uvw.device):
-        stream = torch.cuda.current_stream(uvw.device).cuda_stream
-        _lib.check(_lib.lib().cip_facet_rephase(
-            uvw.data_ptr(), nrow, freq.data_ptr(), nchan, vis.data_ptr() if vis is not None else None,
-            vis_codes[vis.dtype] if vis is not None else _lib.CIP_C64, float(l0), float(m0), stream,
-            uvw_f.data_ptr(), vis_f.data_ptr() if vis_f is not None else None))
+    call(uvw.device, "cip_facet_rephase", uvw, nrow, freq, nchan, *vis_arg(vis), float(l0), float(m0), STREAM,
+         uvw_f, vis_f)
     return uvw_f, vis_f
 
 
@@ -345,24 +256,23 @@ def device_stokes_i(vis4: "torch.Tensor", flags4: "torch.Tensor", wgt4: "torch.T
     bool/uint8 flags and float32 weights -> (vis_i complex64 (nrow, nchan),
     effective weights float32 (nrow, nchan)).
     """
-    _require_gpu()
-    if vis4.dtype != torch.complex64 or wgt4.dtype != torch.float32:
-        raise ValueError("vis4 must be complex64 and wgt4 float32")
-    if vis4.dim() != 3 or vis4.shape[-1] != 4 or tuple(flags4.shape) != tuple(vis4.shape) or \
-            tuple(wgt4.shape) != tuple(vis4.shape):
-        raise ValueError("vis4, flags4, wgt4 must all have shape (nrow, nchan, 4)")
-    fl = flags4.to(torch.uint8) if flags4.dtype != torch.uint8 else flags4
-    for t in (vis4, fl, wgt4):
-        if not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("device_stokes_i needs contiguous device tensors")
-    nrow, nchan = vis4.shape[0], vis4.shape[1]
-    vis_i = torch.empty((nrow, nchan), dtype=torch.complex64, device=vis4.device)
-    eff = torch.empty((nrow, nchan), dtype=torch.float32, device=vis4.device)
-    with torch.cuda.device(vis4.device):
-        stream = torch.cuda.current_stream(vis4.device).cuda_stream
-        _lib.check(_lib.lib().cip_stokes_i(vis4.data_ptr(), fl.data_ptr(), wgt4.data_ptr(), nrow * nchan, stream,
-                                           vis_i.data_ptr(), None, None, eff.data_ptr()))
-    return vis_i, eff
+    require_gpu()
+    return _stokes("cip_stokes_i", vis4, flags4, wgt4)
+
+
+def _stage(uvw, freq, wgt, mask, dev):
+    """ms2dirty's / dirty2ms's uvw, freq (float64) and wgt (its own float32 / float64, zeroed where `mask`
+    is 0; None without either) on `dev`."""
+    uvw_d = to_device(uvw, torch.float64, dev)
+    freq_d = to_device(np.asarray(freq, dtype=np.float64) if not torch.is_tensor(freq) else freq, torch.float64, dev)
+    wgt_d = None
+    if wgt is not None:
+        wdt = torch.float32 if (wgt.dtype in (np.float32, torch.float32)) else torch.float64
+        wgt_d = to_device(wgt, wdt, dev)
+    if mask is not None:
+        m = to_device(np.asarray(mask) if not torch.is_tensor(mask) else mask, torch.bool, dev)
+        wgt_d = m.to(torch.float32) if wgt_d is None else wgt_d * m.to(wgt_d.dtype)
+    return uvw_d, freq_d, wgt_d
 
 
 def ms2dirty(  # pylint: disable=too-many-arguments,unused-argument
@@ -398,28 +308,16 @@ def ms2dirty(  # pylint: disable=too-many-arguments,unused-argument
     shape of ms) zeroes the weights where 0. Output dtype follows ducc:
     float32 for complex64 `ms`, else float64.
     """
-    _require_gpu()
+    require_gpu()
     if npix_x is None or npix_y is None or pixsize_x is None or pixsize_y is None:
         raise TypeError("npix_x, npix_y, pixsize_x and pixsize_y are required")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = target_device(device)
     numpy_in = isinstance(ms, np.ndarray)
     ms_dtype = ms.dtype
     single = ms_dtype in (np.complex64, torch.complex64)
     with torch.cuda.device(dev):
-        uvw_d = _to_device(uvw, torch.float64, dev)
-        freq_d = _to_device(np.asarray(freq, dtype=np.float64) if not torch.is_tensor(freq) else freq,
-                            torch.float64, dev)
-        vis_d = _to_device(ms, torch.complex64 if single else torch.complex128, dev)
-        wgt_d = None
-        if wgt is not None:
-            wdt = torch.float32 if (wgt.dtype in (np.float32, torch.float32)) else torch.float64
-            wgt_d = _to_device(wgt, wdt, dev)
-        if mask is not None:
-            m = _to_device(np.asarray(mask) if not torch.is_tensor(mask) else mask, torch.bool, dev)
-            if wgt_d is None:
-                wgt_d = m.to(torch.float32)
-            else:
-                wgt_d = wgt_d * m.to(wgt_d.dtype)
+        uvw_d, freq_d, wgt_d = _stage(uvw, freq, wgt, mask, dev)
+        vis_d = to_device(ms, torch.complex64 if single else torch.complex128, dev)
         dirty, params = device_ms2dirty(
             uvw_d, freq_d, vis_d, wgt_d, int(npix_x), int(npix_y), float(pixsize_x),
             float(pixsize_y), epsilon=epsilon, support=support, do_wstacking=do_wstacking,
@@ -459,49 +357,32 @@ def device_dirty2ms(
     same uvw / freq / geometry on this thread runs through that invert's tile
     plan. Supports 4..16 only; `dirty` is not modified.
     """
-    vis_codes, wgt_codes = _codes()
     if out_dtype is None:
         out_dtype = torch.complex128
-    nrow = uvw.shape[0]
-    nchan = freq.shape[0]
-    if tuple(uvw.shape) != (nrow, 3):
-        raise ValueError("uvw must have shape (nrow, 3)")
-    if uvw.dtype != torch.float64 or freq.dtype != torch.float64:
-        raise ValueError("uvw and freq must be float64")
-    if dirty.dim() != 2 or dirty.dtype != torch.float64:
+    nrow, nchan = check_rows(uvw, freq, "device_dirty2ms inputs")
+    dev = uvw.device
+    if dirty.dim() != 2:
         raise ValueError(f"dirty must be a float64 (npix_x, npix_y) image, got {dirty.dtype} "
                          f"{tuple(dirty.shape)}")
-    if wgt is not None and wgt.dtype not in wgt_codes:
-        raise ValueError(f"wgt dtype must be float32/float64, got {wgt.dtype}")
-    if wgt is not None and tuple(wgt.shape) != (nrow, nchan):
-        raise ValueError(f"wgt must have shape ({nrow}, {nchan})")
-    for t in (uvw, freq, dirty) + ((wgt,) if wgt is not None else ()):
-        _check_device_tensor(t, uvw.device, "device_dirty2ms inputs")
+    check_array(dirty, (torch.float64,), None, dev, "dirty")
+    wgt_args = wgt_arg(wgt)
+    if wgt is not None:
+        check_array(wgt, WGT_DTYPES, (nrow, nchan), dev, "wgt")
     if out is None:
         if subtract:
             raise ValueError("subtract=True needs `out` holding the visibilities to subtract from")
-        if out_dtype not in vis_codes:
+        if out_dtype not in VIS_DTYPES:
             raise ValueError(f"out_dtype must be complex64/complex128, got {out_dtype}")
-        out = torch.empty((nrow, nchan), dtype=out_dtype, device=uvw.device)
-    else:
-        # the library writes nrow * nchan cells through the raw pointer
-        if out.dtype not in vis_codes or tuple(out.shape) != (nrow, nchan):
-            raise ValueError(f"out must be complex64/complex128 of shape ({nrow}, {nchan}), "
-                             f"got {out.dtype} {tuple(out.shape)}")
-        _check_device_tensor(out, uvw.device, "out")
+        out = torch.empty((nrow, nchan), dtype=out_dtype, device=dev)
+    else:  # the library writes nrow * nchan cells through the raw pointer
+        check_array(out, VIS_DTYPES, (nrow, nchan), dev, "out")
     params = _lib.GridderParams()
-    with torch.cuda.device(uvw.device):
-        stream = torch.cuda.current_stream(uvw.device).cuda_stream
-        rc = _lib.lib().cip_dirty2ms(
-            uvw.data_ptr(), nrow, freq.data_ptr(), nchan, dirty.data_ptr(), int(dirty.shape[0]),
-            int(dirty.shape[1]), float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
-            (_lib.CIP_WSTACKING if do_wstacking else 0)
-            | (_lib.CIP_SUBTRACT if subtract else 0)
-            | (_lib.CIP_REUSE_PLAN if reuse_plan else 0),
-            wgt.data_ptr() if wgt is not None else None,
-            wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE,
-            stream, out.data_ptr(), vis_codes[out.dtype], params)
-    _lib.check(rc)
+    call(dev, "cip_dirty2ms", uvw, nrow, freq, nchan, dirty, int(dirty.shape[0]), int(dirty.shape[1]),
+         float(pixsize_x), float(pixsize_y), float(epsilon), int(support or 0),
+         (_lib.CIP_WSTACKING if do_wstacking else 0)
+         | (_lib.CIP_SUBTRACT if subtract else 0)
+         | (_lib.CIP_REUSE_PLAN if reuse_plan else 0),
+         *wgt_args, STREAM, *vis_arg(out), params)
     return out, params
 
 
@@ -532,27 +413,15 @@ def dirty2ms(  # pylint: disable=too-many-arguments,unused-argument
     Output dtype follows ducc: complex64 for a float32 `dirty`, else
     complex128; the arithmetic is fp64 either way.
     """
-    _require_gpu()
+    require_gpu()
     if pixsize_x is None or pixsize_y is None:
         raise TypeError("pixsize_x and pixsize_y are required")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = target_device(device)
     numpy_in = isinstance(dirty, np.ndarray)
     single = dirty.dtype in (np.float32, torch.float32)
     with torch.cuda.device(dev):
-        uvw_d = _to_device(uvw, torch.float64, dev)
-        freq_d = _to_device(np.asarray(freq, dtype=np.float64) if not torch.is_tensor(freq) else freq,
-                            torch.float64, dev)
-        dirty_d = _to_device(dirty, torch.float64, dev)
-        wgt_d = None
-        if wgt is not None:
-            wdt = torch.float32 if (wgt.dtype in (np.float32, torch.float32)) else torch.float64
-            wgt_d = _to_device(wgt, wdt, dev)
-        if mask is not None:
-            m = _to_device(np.asarray(mask) if not torch.is_tensor(mask) else mask, torch.bool, dev)
-            if wgt_d is None:
-                wgt_d = m.to(torch.float32)
-            else:
-                wgt_d = wgt_d * m.to(wgt_d.dtype)
+        uvw_d, freq_d, wgt_d = _stage(uvw, freq, wgt, mask, dev)
+        dirty_d = to_device(dirty, torch.float64, dev)
         vis, params = device_dirty2ms(
             uvw_d, freq_d, dirty_d, wgt_d, float(pixsize_x), float(pixsize_y), epsilon=epsilon,
             support=support, do_wstacking=do_wstacking,

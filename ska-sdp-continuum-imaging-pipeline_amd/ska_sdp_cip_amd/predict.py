@@ -8,7 +8,8 @@ from __future__ import annotations
 
 from typing import Optional
 
-from .gridder import _require_gpu, device_dirty2ms, dirty2ms
+from ._call import require_gpu
+from .gridder import device_dirty2ms, dirty2ms
 from .invert import DO_WSTACKING, EPSILON, pixel_size_lm
 
 
@@ -55,7 +56,7 @@ def device_residual(
     (CIP_SUBTRACT). Returns a new tensor, or `vis` itself updated in place
     with `inplace=True`. `wgt=None`: plain `vis - model`.
     """
-    _require_gpu()
+    require_gpu()
     out = vis if inplace else vis.clone()
     device_dirty2ms(uvw, freq, model_image, wgt, pixsize, pixsize, epsilon=epsilon, support=support,
                     do_wstacking=do_wstacking, out=out, subtract=True, reuse_plan=reuse_plan)

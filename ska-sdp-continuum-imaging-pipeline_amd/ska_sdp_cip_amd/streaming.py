@@ -27,7 +27,7 @@ from typing import Callable, Iterable, Optional, Sequence
 import numpy as np
 
 from .accumulate import GridAccumulator, merge_w_ranges, w_range_rows, w_range_slices
-from .gridder import _require_gpu
+from ._call import require_gpu
 from .invert import EPSILON, pixel_size_lm
 from .uvw_tiling.tile import Tile
 
@@ -178,7 +178,7 @@ def invert_tile_files(
     `use_weights=False` ignores the key. In w-stacking mode the w range of all
     files is read first (their uvw and channel ranges only) unless given.
     """
-    _require_gpu()
+    require_gpu()
     paths = [Path(p) for p in paths]
     freq = np.asarray(channel_freqs, dtype=np.float64)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -337,7 +337,7 @@ def invert_measurement_set_streamed(
     planes with Stokes I formed inside the gridder (`add_ms_stokes_i`).
     Returns the normalised image as float32 numpy (N, N), like the reference.
     """
-    _require_gpu()
+    require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     freq = np.asarray(ms_reader.channel_frequencies(), dtype=np.float64)
     nrow = ms_reader.num_data_rows

@@ -37,9 +37,11 @@ import ctypes
 
 import numpy as np
 
+from . import _lib
+from ._call import STREAM, call, require_gpu, target_device, vis_arg, wgt_arg
+
 SPEED_OF_LIGHT = 299792458.0
 COL_BLOCK = 4  # pass-A output block width (cip_fft.hip kColBlock)
-ctypes_i64 = ctypes.c_int64
 
 try:
     import torch
@@ -101,18 +103,12 @@ def _on_device(t) -> bool:
 def _gridder_params(params):
     """The ctypes cip_gridder_params of `params` (a GridderParams, or any object
     with its fields - the CPU tests' stand-in)."""
-    from . import _lib  # pylint: disable=import-outside-toplevel
-
     if isinstance(params, _lib.GridderParams):
         return params
     out = _lib.GridderParams()
     for name, _ in _lib.GridderParams._fields_:
         setattr(out, name, type(getattr(out, name))(getattr(params, name, 32 if name == "tile" else 0)))
     return out
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def strip_histogram(uvw, freq, params, pixsize_x: float, pixsize_y: float):
@@ -123,13 +119,10 @@ def strip_histogram(uvw, freq, params, pixsize_x: float, pixsize_y: float):
     CPU tensors: the torch restatement below."""
     nu, nv, W = int(params.nu), int(params.nv), int(params.support)
     if _on_device(uvw):
-        from . import _lib  # pylint: disable=import-outside-toplevel
-
         hist = torch.empty(2 * nv, dtype=torch.int64, device=uvw.device)
         uvw_c, f_c = uvw.contiguous().to(torch.float64), freq.contiguous().to(torch.float64)
-        _lib.check(_lib.lib().cip_strip_histogram(uvw_c.data_ptr(), int(uvw_c.shape[0]), f_c.data_ptr(),
-                                                  int(f_c.shape[0]), _gridder_params(params), float(pixsize_x),
-                                                  float(pixsize_y), _stream(uvw_c), hist.data_ptr()))
+        call(uvw.device, "cip_strip_histogram", uvw_c, int(uvw_c.shape[0]), f_c, int(f_c.shape[0]),
+             _gridder_params(params), float(pixsize_x), float(pixsize_y), STREAM, hist)
         return hist[:nv], hist[nv:]
     fx = freq / SPEED_OF_LIGHT
     vis = torch.zeros(nv, dtype=torch.int64, device=uvw.device)
@@ -250,26 +243,16 @@ def _split_device(uvw, freq, params, pixsize_y: float, y0: int, y1: int, vis=Non
     """cip_strip_split: (slice_uvw, c0, c1 (int32), rows (int64), vis, wgt)
     of the strip [y0, y1) - one count pass + scans, then one emit pass that
     writes the slices and gathers the strip's visibilities (when given)."""
-    from . import _lib  # pylint: disable=import-outside-toplevel
-    from .gridder import _codes  # pylint: disable=import-outside-toplevel
-
     dev = uvw.device
     uvw_c, f_c = uvw.contiguous().to(torch.float64), freq.contiguous().to(torch.float64)
     nrow, nchan = int(uvw_c.shape[0]), int(f_c.shape[0])
-    prm = _gridder_params(params)
-    vis_codes, wgt_codes = _codes()
     if vis is not None:
         vis = vis.reshape(nrow, nchan).contiguous()
         wgt = None if wgt is None else wgt.reshape(nrow, nchan).contiguous()
-    vp = vis.data_ptr() if vis is not None else None
-    vc = vis_codes[vis.dtype] if vis is not None else _lib.CIP_C64
-    wp = wgt.data_ptr() if wgt is not None else None
-    wc = wgt_codes[wgt.dtype] if wgt is not None else _lib.CIP_NONE
-    counts = (ctypes_i64 * 2)()
-    lib = _lib.lib()
-    args = (uvw_c.data_ptr(), nrow, f_c.data_ptr(), nchan, vp, vc, wp, wc, prm, float(pixsize_y), int(y0), int(y1),
-            _stream(uvw_c), counts)
-    _lib.check(lib.cip_strip_split(*args, None, None, None, None, None, None))
+    counts = (ctypes.c_int64 * 2)()
+    args = (uvw_c, nrow, f_c, nchan, *vis_arg(vis), *wgt_arg(wgt), _gridder_params(params), float(pixsize_y), int(y0),
+            int(y1), STREAM, counts)
+    call(dev, "cip_strip_split", *args, None, None, None, None, None, None)
     ns, nvis = int(counts[0]), int(counts[1])
     suvw = torch.empty((ns, 3), dtype=torch.float64, device=dev)
     c0 = torch.empty(ns, dtype=torch.int32, device=dev)
@@ -277,9 +260,8 @@ def _split_device(uvw, freq, params, pixsize_y: float, y0: int, y1: int, vis=Non
     rows = torch.empty(ns, dtype=torch.int64, device=dev)
     vout = torch.empty(nvis, dtype=vis.dtype, device=dev) if vis is not None else None
     wout = torch.empty(nvis, dtype=wgt.dtype, device=dev) if wgt is not None else None
-    _lib.check(lib.cip_strip_split(*args, suvw.data_ptr(), c0.data_ptr(), c1.data_ptr(), rows.data_ptr(),
-                                   vout.data_ptr() if vout is not None and nvis else None,
-                                   wout.data_ptr() if wout is not None and nvis else None))
+    if ns:  # an empty strip needs no emit pass
+        call(dev, "cip_strip_split", *args, suvw, c0, c1, rows, vout, wout)
     return suvw, c0, c1, rows, vout, wout
 
 
@@ -367,15 +349,11 @@ class HipStripBackend:
 
     def __init__(self, params, pixsize_x: float, pixsize_y: float, npix_x: int, npix_y: int, device=None,
                  rows: Optional[tuple] = None, single_precision_accumulation: bool = False):
-        from . import _lib  # pylint: disable=import-outside-toplevel
-        from .gridder import _require_gpu  # pylint: disable=import-outside-toplevel
-
-        _require_gpu()
-        self._lib = _lib
+        require_gpu()
         self.params = params
         self.px, self.py = float(pixsize_x), float(pixsize_y)
         self.npix_x, self.npix_y = int(npix_x), int(npix_y)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = target_device(device)
         if not _lib.lib().cip_grid_layout(params, self.npix_x, self.npix_y):
             raise ValueError("strips need a grid in the pruned-FFT layout (power-of-two grids)")
         self.nplanes = int(params.nplanes) if int(params.do_wstacking) else 1
@@ -414,19 +392,13 @@ class HipStripBackend:
         self._alloc(strip_buffer_rows(layout, rank))
         return self
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def grid_strip(self, data: StripData, freq):
         """Grid the strip's visibilities; returns (strip buffer (nrows, nu, 2) f64 - (nplanes, nrows, nu, 2)
         with w-stacking -, weight sum (1,) f64)."""
-        from .gridder import _codes  # pylint: disable=import-outside-toplevel
-
         if self.dirty:  # a previous invert did not finish: the buffer may hold partial sums
             self.grid.zero_()
         self.dirty = True
         self._bits_valid = False
-        vis_codes, wgt_codes = _codes()
         sumw = torch.zeros(1, dtype=torch.float64, device=self.device)
         ns = int(data.slice_uvw.shape[0])
         nu, nv = int(self.params.nu), int(self.params.nv)
@@ -435,20 +407,14 @@ class HipStripBackend:
             shape = (self.nplanes, nv // TILE, nu // TILE // 32)
             if self._bits is None or tuple(self._bits.shape) != shape:
                 self._bits = torch.empty(shape, dtype=torch.int32, device=self.device)
-        fn = self._lib.lib().cip_grid_tiles_strip_mask if mask else self._lib.lib().cip_grid_tiles_strip
-        extra = (self._bits.data_ptr(),) if mask else ()
         if ns or mask:
             # an empty strip still writes its mask (the halo rows it receives)
-            self._lib.check(fn(
-                data.slice_uvw.data_ptr() if ns else None, data.chan_start.data_ptr() if ns else None,
-                data.chan_stop.data_ptr() if ns else None, ns,
-                freq.data_ptr(), int(freq.shape[0]), data.vis.data_ptr() if data.nvis else None, data.nvis,
-                vis_codes[data.vis.dtype],
-                data.wgt.data_ptr() if data.wgt is not None and data.nvis else None,
-                wgt_codes[data.wgt.dtype] if data.wgt is not None else self._lib.CIP_NONE,
-                self.params, self.px, self.py, self.npix_x, self.npix_y, self.rows[0], self.rows[1],
-                self._lib.CIP_GRID_ZEROED | (self._lib.CIP_ACC_SINGLE if self.single else 0), self._stream(),
-                self.grid.data_ptr(), sumw.data_ptr(), *extra))
+            vis_ptr, vis_code = vis_arg(data.vis)
+            call(self.device, "cip_grid_tiles_strip_mask" if mask else "cip_grid_tiles_strip",
+                 data.slice_uvw, data.chan_start, data.chan_stop, ns, freq, int(freq.shape[0]), vis_ptr, data.nvis,
+                 vis_code, *wgt_arg(data.wgt), self.params, self.px, self.py, self.npix_x, self.npix_y,
+                 self.rows[0], self.rows[1], _lib.CIP_GRID_ZEROED | (_lib.CIP_ACC_SINGLE if self.single else 0),
+                 STREAM, self.grid, sumw, *((self._bits,) if mask else ()))
         self._bits_valid = mask
         return self.grid, sumw
 
@@ -461,12 +427,11 @@ class HipStripBackend:
         rows (only the dirty tiles' cells are read when the gridded strip's mask is known)."""
         H = torch.empty((self.npix_x // COL_BLOCK, y1 - y0, COL_BLOCK, 2), dtype=torch.float64, device=self.device)
         if self._bits_valid and self.dirty:
-            self._lib.check(self._lib.lib().cip_strip_rows_masked(
-                grid.data_ptr(), self.params, self.npix_x, self.npix_y, int(y0), int(y1), int(self.rows[0]),
-                self._bits[plane].data_ptr(), self._stream(), H.data_ptr()))
+            call(self.device, "cip_strip_rows_masked", grid, self.params, self.npix_x, self.npix_y, int(y0), int(y1),
+                 int(self.rows[0]), self._bits[plane], STREAM, H)
         else:
-            self._lib.check(self._lib.lib().cip_strip_rows(grid.data_ptr(), self.params, self.npix_x, self.npix_y,
-                                                           int(y0), int(y1), self._stream(), H.data_ptr()))
+            call(self.device, "cip_strip_rows", grid, self.params, self.npix_x, self.npix_y, int(y0), int(y1),
+                 STREAM, H)
         return H
 
     def pass_rows_packed(self, grid, y0: int, y1: int, live, count: int, plane: int = 0):
@@ -479,10 +444,8 @@ class HipStripBackend:
         slot = torch.cumsum(live.to(torch.int64), 0).sub_(1)
         slot = torch.where(live, slot, torch.full_like(slot, -1))
         H = torch.empty((self.npix_x // COL_BLOCK, count, COL_BLOCK, 2), dtype=torch.float64, device=self.device)
-        self._lib.check(self._lib.lib().cip_strip_rows_packed(
-            grid.data_ptr(), self.params, self.npix_x, self.npix_y, int(y0), int(y1), int(self.rows[0]),
-            self._bits[plane].data_ptr(), slot.data_ptr(), int(count), self._stream(),
-            H.data_ptr() if count else None))
+        call(self.device, "cip_strip_rows_packed", grid, self.params, self.npix_x, self.npix_y, int(y0), int(y1),
+             int(self.rows[0]), self._bits[plane], slot, int(count), STREAM, H)
         return H
 
     def live_rows(self, h: int, plane: int = 0):
@@ -499,24 +462,21 @@ class HipStripBackend:
     def pass_cols(self, H, i0: int, i1: int, norm=None):
         """Pass B for image rows [i0, i1) from H ((i1 - i0) / 4, nv, 4, 2)."""
         out = torch.empty((i1 - i0, self.npix_y), dtype=torch.float64, device=self.device)
-        self._lib.check(self._lib.lib().cip_strip_cols(H.data_ptr(), self.params, self.npix_x, self.npix_y,
-                                                       int(i0), int(i1), None if norm is None else norm.data_ptr(),
-                                                       self._stream(), out.data_ptr()))
+        call(self.device, "cip_strip_cols", H, self.params, self.npix_x, self.npix_y, int(i0), int(i1), norm, STREAM,
+             out)
         return out
 
     def pass_cols_wplane(self, H, i0: int, i1: int, plane: int, first: bool, acc):
         """Pass B of w plane `plane` for image rows [i0, i1) with its w screen, into acc ((i1 - i0), npix_y)
         f64 (overwritten when `first`)."""
-        self._lib.check(self._lib.lib().cip_strip_cols_wplane(
-            H.data_ptr(), self.params, self.npix_x, self.npix_y, self.px, self.py, int(i0), int(i1), int(plane),
-            int(bool(first)), self._stream(), acc.data_ptr()))
+        call(self.device, "cip_strip_cols_wplane", H, self.params, self.npix_x, self.npix_y, self.px, self.py,
+             int(i0), int(i1), int(plane), int(bool(first)), STREAM, acc)
         return acc
 
     def finish_rows(self, acc, i0: int, i1: int, norm=None):
         """The final w and grid corrections of image rows [i0, i1) (acc, in place), / norm."""
-        self._lib.check(self._lib.lib().cip_strip_wfinal(
-            acc.data_ptr(), self.params, self.npix_x, self.npix_y, self.px, self.py, int(i0), int(i1),
-            None if norm is None else norm.data_ptr(), self._stream()))
+        call(self.device, "cip_strip_wfinal", acc, self.params, self.npix_x, self.npix_y, self.px, self.py, int(i0),
+             int(i1), norm, STREAM)
         return acc
 
 
@@ -666,14 +626,11 @@ def _pack_live(H, live, count: int):
     nb, h = int(H.shape[0]), int(H.shape[1])
     if H.device.type != "cuda":
         return H.index_select(1, torch.nonzero(live).reshape(-1))
-    from . import _lib  # pylint: disable=import-outside-toplevel
-
     H = H.contiguous()
     slot = torch.cumsum(live.to(torch.int64), 0).sub_(1)
     slot = torch.where(live, slot, torch.full_like(slot, -1))
     out = torch.empty((nb, count) + tuple(H.shape[2:]), dtype=H.dtype, device=H.device)
-    _lib.check(_lib.lib().cip_strip_pack_rows(H.data_ptr(), nb, h, _elem_bytes(H), slot.data_ptr(), count,
-                                              torch.cuda.current_stream(H.device).cuda_stream, out.data_ptr()))
+    call(H.device, "cip_strip_pack_rows", H, nb, h, _elem_bytes(H), slot, count, STREAM, out)
     return out
 
 
@@ -688,8 +645,6 @@ def _unpack_rows(recv, nb: int, layout: StripLayout, masks, dtype, stacked=None)
     of each grid row's block 0 and its source's row count - in a handful of
     vectorised ops (`stacked`: the ranks' masks as one (world, >= max rows)
     tensor, when the caller has it)."""
-    from . import _lib  # pylint: disable=import-outside-toplevel
-
     dev = recv.device
     nv, world = layout.nv, layout.world
     hs = [layout.rows(r)[1] - layout.rows(r)[0] for r in range(world)]
@@ -714,9 +669,7 @@ def _unpack_rows(recv, nb: int, layout: StripLayout, masks, dtype, stacked=None)
                       torch.full((nv,), -1, dtype=torch.int64, device=dev))
     stride = cnt[rr]
     H = torch.empty((nb, nv, COL_BLOCK, 2), dtype=dtype, device=dev)
-    _lib.check(_lib.lib().cip_strip_unpack_rows(recv.data_ptr(), nb, nv, 2 * H.element_size(), rec.data_ptr(),
-                                                stride.data_ptr(), torch.cuda.current_stream(dev).cuda_stream,
-                                                H.data_ptr()))
+    call(dev, "cip_strip_unpack_rows", recv, nb, nv, 2 * H.element_size(), rec, stride, STREAM, H)
     return H
 
 

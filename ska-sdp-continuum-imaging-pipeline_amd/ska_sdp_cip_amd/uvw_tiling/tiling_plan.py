@@ -20,7 +20,7 @@ from typing import NamedTuple
 import numpy as np
 from numpy.typing import NDArray
 
-from .. import _lib
+from .._call import STREAM, call
 
 TileCoords = tuple[int, int, int]
 """Tile index of the form (iu, iv, iw) (reference :10-13)."""
@@ -55,20 +55,16 @@ def tile_runs(uvw, tile_size, channel_freqs, *, row_offset: int = 0):
     dev = torch.device("cuda", torch.cuda.current_device())
     uvw_d = torch.from_numpy(uvw).to(dev)
     f_d = torch.from_numpy(freqs).to(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     n = ctypes.c_int64(0)
-    so = _lib.lib()
-    _lib.check(so.cip_tile_runs(uvw_d.data_ptr(), nrow, f_d.data_ptr(), nchan, ts, int(row_offset), stream,
-                                ctypes.byref(n), None, None, None, None))
+    args = (uvw_d, nrow, f_d, nchan, ts, int(row_offset), STREAM, ctypes.byref(n))
+    call(dev, "cip_tile_runs", *args, None, None, None, None)
     total = n.value
     key = torch.empty((max(total, 1), 3), dtype=torch.int64, device=dev)
     row = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
     c0 = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
     c1 = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
     if total:
-        _lib.check(so.cip_tile_runs(uvw_d.data_ptr(), nrow, f_d.data_ptr(), nchan, ts, int(row_offset), stream,
-                                    ctypes.byref(n), key.data_ptr(), row.data_ptr(), c0.data_ptr(),
-                                    c1.data_ptr()))
+        call(dev, "cip_tile_runs", *args, key, row, c0, c1)
     return (key[:total].cpu().numpy(), row[:total].cpu().numpy(), c0[:total].cpu().numpy(),
             c1[:total].cpu().numpy())
 

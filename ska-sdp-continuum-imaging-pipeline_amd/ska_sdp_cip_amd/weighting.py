@@ -23,7 +23,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .gridder import _check_device_tensor, _codes, _require_gpu, _to_device
+from ._call import (STREAM, WGT_DTYPES, call, check_array, check_rows, require_gpu, target_device, to_device,
+                    wgt_arg)
 
 try:
     import torch
@@ -48,37 +49,21 @@ def briggs_f2(robust: float, sum_w: float, sum_d2: float) -> float:
 
 def _check_columns(uvw, freq, wgt, what):
     """Shapes, dtypes and placement of one chunk; returns (nrow, nchan, wgt pointer, wgt code)."""
-    _, wgt_codes = _codes()
-    nrow, nchan = int(uvw.shape[0]), int(freq.shape[0])
-    if tuple(uvw.shape) != (nrow, 3) or freq.dim() != 1:
-        raise ValueError("uvw must have shape (nrow, 3) and freq (nchan,)")
-    if uvw.dtype != torch.float64 or freq.dtype != torch.float64:
-        raise ValueError("uvw and freq must be float64")
-    _check_device_tensor(uvw, uvw.device, what)
-    _check_device_tensor(freq, uvw.device, what)
-    if wgt is None:
-        return nrow, nchan, None, _lib.CIP_NONE
-    if wgt.dtype not in wgt_codes:
-        raise ValueError(f"wgt dtype must be float32/float64, got {wgt.dtype}")
-    if tuple(wgt.shape) != (nrow, nchan):
-        raise ValueError(f"wgt must have shape ({nrow}, {nchan}), got {tuple(wgt.shape)}")
-    _check_device_tensor(wgt, uvw.device, what)
-    return nrow, nchan, wgt.data_ptr(), wgt_codes[wgt.dtype]
+    nrow, nchan = check_rows(uvw, freq, what)
+    wgt_args = wgt_arg(wgt)
+    if wgt is not None:
+        check_array(wgt, WGT_DTYPES, (nrow, nchan), uvw.device, "wgt")
+    return nrow, nchan, *wgt_args
 
 
 def _check_out(out, wgt, nrow, nchan, device):
-    """The output tensor (allocated in the dtype of `wgt`, float64 without weights) and its code."""
-    _, wgt_codes = _codes()
+    """The output tensor (allocated in the dtype of `wgt`, float64 without weights)."""
     if out is None:
-        out = torch.empty((nrow, nchan), dtype=torch.float64 if wgt is None else wgt.dtype, device=device)
-    else:
-        if out.dtype not in wgt_codes or tuple(out.shape) != (nrow, nchan):
-            raise ValueError(f"out must be float32/float64 of shape ({nrow}, {nchan}), "
-                             f"got {out.dtype} {tuple(out.shape)}")
-        _check_device_tensor(out, device, "out")
-        if wgt is not None and out.data_ptr() == wgt.data_ptr() and out.dtype != wgt.dtype:
-            raise ValueError("in place needs out.dtype == wgt.dtype")
-    return out, wgt_codes[out.dtype]
+        return torch.empty((nrow, nchan), dtype=torch.float64 if wgt is None else wgt.dtype, device=device)
+    check_array(out, WGT_DTYPES, (nrow, nchan), device, "out")
+    if wgt is not None and out.data_ptr() == wgt.data_ptr() and out.dtype != wgt.dtype:
+        raise ValueError("in place needs out.dtype == wgt.dtype")
+    return out
 
 
 def device_imaging_weights(
@@ -110,17 +95,12 @@ def device_imaging_weights(
     mode = _mode(weighting)
     if mode == _lib.CIP_WEIGHT_NATURAL:
         return wgt, {}
-    _require_gpu()
+    require_gpu()
     nrow, nchan, wgt_ptr, wgt_code = _check_columns(uvw, freq, wgt, "device_imaging_weights inputs")
-    out, out_code = _check_out(out, wgt, nrow, nchan, uvw.device)
+    out = _check_out(out, wgt, nrow, nchan, uvw.device)
     info = _lib.WeightInfo()
-    with torch.cuda.device(uvw.device):
-        stream = torch.cuda.current_stream(uvw.device).cuda_stream
-        rc = _lib.lib().cip_imaging_weights(
-            uvw.data_ptr(), nrow, freq.data_ptr(), nchan, wgt_ptr, wgt_code, int(npix_x), int(npix_y),
-            float(pixsize_x), float(pixsize_y), mode, float(robust), stream, out.data_ptr(), out_code,
-            ctypes.byref(info))
-    _lib.check(rc)
+    call(uvw.device, "cip_imaging_weights", uvw, nrow, freq, nchan, wgt_ptr, wgt_code, int(npix_x), int(npix_y),
+         float(pixsize_x), float(pixsize_y), mode, float(robust), STREAM, *wgt_arg(out), ctypes.byref(info))
     return out, info.as_dict()
 
 
@@ -133,15 +113,15 @@ def imaging_weights(uvw, freq, wgt, npix_x, npix_y, pixsize_x, pixsize_y, *, wei
     """
     if _mode(weighting) == _lib.CIP_WEIGHT_NATURAL:
         return wgt, {}
-    _require_gpu()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    require_gpu()
+    dev = target_device(device)
     numpy_in = isinstance(uvw, np.ndarray)
     with torch.cuda.device(dev):
         wgt_d = None
         if wgt is not None:
             f32 = (wgt.dtype == np.float32) if isinstance(wgt, np.ndarray) else (wgt.dtype == torch.float32)
-            wgt_d = _to_device(wgt, torch.float32 if f32 else torch.float64, dev)
-        out, info = device_imaging_weights(_to_device(uvw, torch.float64, dev), _to_device(freq, torch.float64, dev),
+            wgt_d = to_device(wgt, torch.float32 if f32 else torch.float64, dev)
+        out, info = device_imaging_weights(to_device(uvw, torch.float64, dev), to_device(freq, torch.float64, dev),
                                            wgt_d, npix_x, npix_y, pixsize_x, pixsize_y, weighting=weighting,
                                            robust=robust)
     return (out.cpu().numpy() if numpy_in else out), info
@@ -165,7 +145,7 @@ class WeightDensity:
     """
 
     def __init__(self, npix_x, npix_y, pixsize_x, pixsize_y, wmax, nvis_max, device):
-        _require_gpu()
+        require_gpu()
         self.grid = _lib.weight_grid(npix_x, npix_y, pixsize_x, pixsize_y, wmax, nvis_max)
         self.device = torch.device(device)
         self.density = torch.zeros(self.grid.density_shape, dtype=torch.int64, device=self.device)
@@ -174,20 +154,14 @@ class WeightDensity:
         self.f2 = 0.0
         self.stats = None
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def add_ms(self, uvw, freq, wgt) -> dict:
         """Adds one chunk's weights; returns that chunk's counts."""
         nrow, nchan, wgt_ptr, wgt_code = _check_columns(uvw, freq, wgt, "WeightDensity.add_ms inputs")
         if uvw.device != self.device:
             raise ValueError(f"chunk on {uvw.device}, density on {self.device}")
         counts = (ctypes.c_int64 * 3)()
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().cip_weight_density(uvw.data_ptr(), nrow, freq.data_ptr(), nchan, wgt_ptr, wgt_code,
-                                               ctypes.byref(self.grid), self._stream(), self.density.data_ptr(),
-                                               counts)
-        _lib.check(rc)
+        call(self.device, "cip_weight_density", uvw, nrow, freq, nchan, wgt_ptr, wgt_code, ctypes.byref(self.grid),
+             STREAM, self.density, counts)
         self.counts["n_added"] += int(counts[0])
         self.counts["n_outside"] += int(counts[1])
         self.mode = None  # the statistics are stale
@@ -208,9 +182,7 @@ class WeightDensity:
         if not math.isfinite(float(robust)):
             raise ValueError("robust must be finite")
         stats = (ctypes.c_double * 3)()
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().cip_weight_stats(self.density.data_ptr(), ctypes.byref(self.grid), self._stream(), stats)
-        _lib.check(rc)
+        call(self.device, "cip_weight_stats", self.density, ctypes.byref(self.grid), STREAM, stats)
         self.f2 = briggs_f2(robust, stats[0], stats[1]) if mode == _lib.CIP_WEIGHT_BRIGGS else 0.0
         if not math.isfinite(self.f2):
             raise ValueError("robust gives no finite f2")
@@ -226,10 +198,7 @@ class WeightDensity:
         nrow, nchan, wgt_ptr, wgt_code = _check_columns(uvw, freq, wgt, "WeightDensity.apply inputs")
         if uvw.device != self.device:
             raise ValueError(f"chunk on {uvw.device}, density on {self.device}")
-        out, out_code = _check_out(out, wgt, nrow, nchan, self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().cip_weight_apply(uvw.data_ptr(), nrow, freq.data_ptr(), nchan, wgt_ptr, wgt_code,
-                                             self.density.data_ptr(), ctypes.byref(self.grid), self.mode, self.f2,
-                                             self._stream(), out.data_ptr(), out_code)
-        _lib.check(rc)
+        out = _check_out(out, wgt, nrow, nchan, self.device)
+        call(self.device, "cip_weight_apply", uvw, nrow, freq, nchan, wgt_ptr, wgt_code, self.density,
+             ctypes.byref(self.grid), self.mode, self.f2, STREAM, *wgt_arg(out))
         return out

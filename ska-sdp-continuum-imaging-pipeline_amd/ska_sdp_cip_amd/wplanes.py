@@ -28,6 +28,11 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
+from ._call import require_gpu
+from .accumulate import w_range_rows
+from .gridder import device_ms2dirty
+
 SPEED_OF_LIGHT = 299792458.0
 # FFT work of one plane in units of "visibility feeds" (one visibility gridded
 # onto one plane) per grid cell, measured at C3 with the reference's call
@@ -97,9 +102,7 @@ class HipWPlaneBackend:
 
     def __init__(self, uvw, freq, vis, wgt, npix_x: int, npix_y: int, pixsize_x: float, pixsize_y: float, *,
                  epsilon: float = 1e-4, support: Optional[int] = None, single_precision_accumulation: bool = False):
-        from .gridder import _require_gpu  # pylint: disable=import-outside-toplevel
-
-        _require_gpu()
+        require_gpu()
         self.args = (uvw, freq, vis, wgt, int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y))
         self.kw = dict(epsilon=epsilon, support=support, do_wstacking=True,
                        single_precision_accumulation=single_precision_accumulation)
@@ -107,9 +110,6 @@ class HipWPlaneBackend:
 
     def params(self):
         """The whole stack's parameters (the w range of all visibilities)."""
-        from . import _lib  # pylint: disable=import-outside-toplevel
-        from .accumulate import w_range_rows  # pylint: disable=import-outside-toplevel
-
         uvw, freq, _, _, nx, ny, px, py = self.args
         wmin, wmax = w_range_rows(uvw.cpu().numpy(), freq.cpu().numpy())
         return _lib.choose_params(nx, ny, px, py, self.kw["epsilon"], self.kw["support"] or 0, True, wmin, wmax)
@@ -117,14 +117,10 @@ class HipWPlaneBackend:
     def plane_group(self, params=None) -> int:
         """The library's w-plane group for these parameters (cip_plane_group):
         pass it to `split_planes` so no rank boundary falls inside a group."""
-        from . import _lib  # pylint: disable=import-outside-toplevel
-
         return _lib.plane_group(self.params() if params is None else params,
                                 bool(self.kw["single_precision_accumulation"]))
 
     def __call__(self, planes, out=None, sum_weights=None):
-        from .gridder import device_ms2dirty  # pylint: disable=import-outside-toplevel
-
         if sum_weights is None:
             sum_weights = torch.zeros(1, dtype=torch.float64, device=self.device)
         img, _ = device_ms2dirty(*self.args, out=out, sum_weights=sum_weights, planes=tuple(planes), **self.kw)

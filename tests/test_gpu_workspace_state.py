@@ -48,13 +48,12 @@ def test_grid_zeroed_flag_ignores_unaligned_planes(gpu_device):
     # CIP_GRID_ZEROED's private-cell stores are 16-byte: planes that are only
     # 8-byte aligned take the atomic path (same values) instead of faulting
     from ska_sdp_cip_amd import _lib
-    from ska_sdp_cip_amd.gridder import _codes
+    from ska_sdp_cip_amd._call import vis_arg, wgt_arg
 
     npix = 8192  # a 16384^2 grid: the size where the flush stores are on
     nrow, nchan = 400, 4
     uvw, f, vis, w, px = _inputs(gpu_device, nrow, nchan, 512, 5)
     prm = _lib.choose_params(npix, npix, px / 16, px / 16, 1e-4, 8)
-    vc, wc = _codes()
     n = 2 * prm.nu * prm.nv
     out = []
     for off in (0, 1):  # 16-byte aligned, then shifted by one double
@@ -62,8 +61,8 @@ def test_grid_zeroed_flag_ignores_unaligned_planes(gpu_device):
         planes = store[off:off + n]
         assert (planes.data_ptr() % 16 == 0) == (off == 0)
         sw = torch.zeros(1, dtype=torch.float64, device=gpu_device)
-        _lib.check(_lib.lib().cip_grid_ms(uvw.data_ptr(), nrow, f.data_ptr(), nchan, vis.data_ptr(), vc[vis.dtype],
-                                          w.data_ptr(), wc[w.dtype], prm, px / 16, px / 16, npix, npix,
+        _lib.check(_lib.lib().cip_grid_ms(uvw.data_ptr(), nrow, f.data_ptr(), nchan, *vis_arg(vis), *wgt_arg(w),
+                                          prm, px / 16, px / 16, npix, npix,
                                           _lib.CIP_GRID_ZEROED, torch.cuda.current_stream().cuda_stream,
                                           planes.data_ptr(), sw.data_ptr()))
         torch.cuda.synchronize()
