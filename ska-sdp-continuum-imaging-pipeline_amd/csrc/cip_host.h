@@ -138,6 +138,13 @@ struct Workspace {
   std::vector<double> saved_key;
   cip_gridder_params saved_p;
   PlanResult saved_plan;
+  // cip_restore never waits for the device, so its tap table goes up through
+  // pinned staging of its own (`pinned` is rewritten by the next call): the
+  // (a, b, c, R) of the table on the device, and the event behind the last
+  // upload, which the next upload waits for before it rewrites the staging
+  void* restore_pinned = nullptr;
+  hipEvent_t ev_restore = nullptr;
+  std::vector<double> restore_key;
 };
 
 // ---- cip_workspace.hip ----

@@ -80,6 +80,8 @@ static void destroy_workspace(Workspace* ws) {
     if (kv.second.ptr) (void)hipFree(kv.second.ptr);
   for (auto& p : ws->plans) (void)hipfftDestroy(p.h);
   if (ws->pinned) (void)hipHostFree(ws->pinned);
+  if (ws->restore_pinned) (void)hipHostFree(ws->restore_pinned);
+  if (ws->ev_restore) (void)hipEventDestroy(ws->ev_restore);
   if (ws->side) {
     (void)hipStreamSynchronize(ws->side);
     (void)hipStreamDestroy(ws->side);

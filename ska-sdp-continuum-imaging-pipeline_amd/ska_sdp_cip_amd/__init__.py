@@ -6,9 +6,10 @@ Public API mirrors `/root/reference/src/ska_sdp_cip/__init__.py:1-10`
 `dask_invert_measurement_set`, `__version__`) plus the drop-in gridder
 `ms2dirty` (replaces `ducc0.wgridder.ms2dirty`), its adjoint `dirty2ms`
 (`ducc0.wgridder.dirty2ms`; `predict.py` wraps it), the minor and major cycle
-built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), uniform
-and Briggs imaging weights (`weighting.py`, `cip_imaging_weights`) and the
-`uvw_tiling` package.
+built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), the
+clean beam and the restored image (`restore.py`, `cip_beam_fit`,
+`cip_restore`), uniform and Briggs imaging weights (`weighting.py`,
+`cip_imaging_weights`) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -23,6 +24,9 @@ from .invert import (  # noqa: E402
 )
 from .predict import device_residual, ducc_predict  # noqa: E402
 from .deconvolve import device_hogbom_clean, device_major_cycles, hogbom_clean  # noqa: E402
+# `restore.restore` (numpy in -> numpy out) stays in its module: exported here
+# it would hide the module of the same name
+from .restore import beam_from_fwhm, beam_taps, beam_to_sky, device_fit_beam, device_restore  # noqa: E402
 from .weighting import WeightDensity, device_imaging_weights, imaging_weights  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
@@ -63,4 +67,9 @@ __all__ = [
     "imaging_weights",
     "device_imaging_weights",
     "WeightDensity",
+    "device_restore",
+    "device_fit_beam",
+    "beam_from_fwhm",
+    "beam_taps",
+    "beam_to_sky",
 ]

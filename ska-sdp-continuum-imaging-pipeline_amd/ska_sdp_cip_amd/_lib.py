@@ -1,5 +1,5 @@
 """
-ctypes binding of libcip_hip.so (C ABI: include/cip.h).
+ctypes binding of libcip_hip.so (C ABI: include/cip.h and include/cip_restore.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -126,6 +126,29 @@ class WeightInfo(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Beam(ctypes.Structure):
+    """Mirror of `cip_beam` (include/cip_restore.h)."""
+
+    _fields_ = [
+        ("a", ctypes.c_double),
+        ("b", ctypes.c_double),
+        ("c", ctypes.c_double),
+        ("fwhm_major", ctypes.c_double),
+        ("fwhm_minor", ctypes.c_double),
+        ("pa", ctypes.c_double),
+        ("n_fit", ctypes.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# CIP_RESTORE_MAX_RADIUS, CIP_BEAM_FIT_RADIUS and CIP_BEAM_FIT_CUT of include/cip_restore.h
+RESTORE_MAX_RADIUS = 32
+BEAM_FIT_RADIUS = 8
+BEAM_FIT_CUT = 0.35
+
 _LIB = None
 
 _vp = ctypes.c_void_p
@@ -193,6 +216,17 @@ PROTOTYPES = {
 }
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
+# The same for include/cip_restore.h, the second header of the C ABI.
+_beam = ctypes.POINTER(Beam)
+RESTORE_PROTOTYPES = {
+    "cip_beam_from_fwhm": (_i32, [_f64, _f64, _f64, _beam]),
+    "cip_beam_fit_window": (_i32, [_pf64, _i64, _f64, _beam]),
+    "cip_beam_fit": (_i32, [_vp, _i64, _i64, _i64, _i64, _f64, _i64, _vp, _beam]),
+    "cip_beam_radius": (_i32, [_beam, _f64]),
+    "cip_beam_taps": (_i32, [_beam, _i64, _pf64]),
+    "cip_restore": (_i32, [_vp, _vp, _i64, _i64, _beam, _i64, _vp, _vp]),
+}
+
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
@@ -207,7 +241,7 @@ def lib() -> ctypes.CDLL:
             "(make -C ska-sdp-continuum-imaging-pipeline_amd/csrc)"
         )
     so = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

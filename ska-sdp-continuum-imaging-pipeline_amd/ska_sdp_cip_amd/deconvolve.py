@@ -21,6 +21,7 @@ from ._call import STREAM, call, check_array, require_gpu, target_device, to_dev
 from .gridder import device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .predict import device_residual
+from .restore import device_fit_beam, device_restore
 from .weighting import device_imaging_weights
 
 try:
@@ -158,6 +159,8 @@ def device_major_cycles(
     support: Optional[int] = None,
     weighting: str = "natural",
     robust: float = 0.0,
+    restore: bool = False,
+    beam: Optional[dict] = None,
 ):
     """
     Major cycles on device-resident data (an `npix` x `npix` image with pixels
@@ -182,6 +185,10 @@ def device_major_cycles(
     start of each cycle run), `components` (count per cycle) and `stop_reason`
     ("threshold": a cycle started at or below it; "n_major": the cycles ran
     out; "empty": the mask allows no pixel).
+
+    `restore=True` adds `beam` (the clean beam, `restore.device_fit_beam` of
+    the loop's PSF unless `beam` is passed) and `restored` (the final model
+    convolved with it plus the final residual, `restore.device_restore`).
     """
     require_gpu()
     npix = int(npix)
@@ -211,5 +218,9 @@ def device_major_cycles(
         vis_res = device_residual(uvw, freq, vis, model, pixsize, None, reuse_plan=True, **kw)
         device_ms2dirty(uvw, freq, vis_res, wgt, npix, npix, pixsize, pixsize, normalise=True, reuse_plan=True,
                         out=residual, **kw)
-    return {"model": model, "residual": residual, "psf": psf, "peaks": peaks, "components": components,
-            "stop_reason": stop_reason}
+    result = {"model": model, "residual": residual, "psf": psf, "peaks": peaks, "components": components,
+              "stop_reason": stop_reason}
+    if restore:
+        result["beam"] = device_fit_beam(psf) if beam is None else dict(beam)
+        result["restored"] = device_restore(model, residual, result["beam"])
+    return result

@@ -29,6 +29,13 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     bincount with weights, gather, divide) and whether its
                     weights agree; the mean run of equal cells a lane merges
                     into one atomic add
+  --mode restore    device_restore on an 8192^2 image with the beam fitted to a
+                    PSF from device_ms2dirty(psf=True) on bench.py's C3 inputs:
+                    a sparse model (10 000 seeded non-zeros) and a dense 512^2
+                    patch, best of --repeat around a synchronised call, beside
+                    torch conv2d in fp64 with the same taps plus the add and a
+                    torch fft2 convolution on the same device in the same run;
+                    also written to profiles/restore_c3.json
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -273,10 +280,118 @@ def weights(args):
             "apply_GBs_at_8B_per_vis": round(8.0 * nvis / ms_apply / 1e6, 1)}
 
 
+def restore(args):
+    """ms per device_restore call (sparse and dense model) and per torch conv2d / fft2 restatement."""
+    import torch
+    import torch.nn.functional as F
+
+    sys.path.insert(0, str(ROOT))
+    import bench  # the flagship workload's own inputs
+
+    from ska_sdp_cip_amd import _lib, gridder, restore as rst
+
+    dev = torch.device("cuda", 0)
+    cfg = bench.CONFIGS[args.config]
+    uvw, freq, _, wgt, px, _, _ = bench.make_inputs(cfg, 0, 1, dev)
+    psf, _ = gridder.device_ms2dirty(uvw, freq, None, wgt, cfg["npix"], cfg["npix"], px, px, support=8, psf=True,
+                                     normalise=True)
+    c = cfg["npix"] // 2
+    psf = psf[c - 64:c + 65, c - 64:c + 65].contiguous()  # the cut keeps the peak at the patch's centre
+    del uvw, wgt
+    _lib.lib().cip_release_workspace()  # the invert's grid is not needed any more
+    beam = rst.device_fit_beam(psf)
+    try:
+        radius = rst.beam_radius(beam)
+    except ValueError:  # wider than 12.5 px: the largest support, the beam cut off above 1e-8
+        radius = _lib.RESTORE_MAX_RADIUS
+    taps =torch.from_numpy(rst.beam_taps(beam, radius)).to(dev)
+    n = args.restore_npix
+    g = torch.Generator(device=dev)
+    g.manual_seed(20241020)
+    residual = torch.randn((n, n), dtype=torch.float64, device=dev, generator=g)
+    out = torch.empty_like(residual)
+
+    def best(fn):
+        fn()  # warm-up: workspace, the tap table, torch's own plans
+        times = []
+        for _ in range(args.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return min(times) * 1e3
+
+    def torch_conv(model, dst):
+        # dense fp64 conv2d in strips of rows: the unfolded strip stays under ~4 GB
+        w = taps.flip(0, 1)[None, None]
+        strip = max(32, int(4e9 / (8.0 * n * taps.numel())))
+        for i0 in range(0, n, strip):
+            i1 = min(n, i0 + strip)
+            lo, hi = max(0, i0 - radius), min(n, i1 + radius)
+            part = F.pad(model[lo:hi], (radius, radius, radius - (i0 - lo), radius - (hi - i1)))
+            dst[i0:i1] = F.conv2d(part[None, None], w)[0, 0] + residual[i0:i1]
+
+    kernel = torch.zeros((n, n), dtype=torch.float64, device=dev)
+    kernel[:2 * radius + 1, :2 * radius + 1] = taps
+    kernel_f = torch.fft.rfft2(torch.roll(kernel, (-radius, -radius), (0, 1)))  # not timed: it belongs to the beam
+    del kernel
+
+    def torch_fft(model, dst):
+        torch.add(torch.fft.irfft2(torch.fft.rfft2(model) * kernel_f, s=(n, n)), residual, out=dst)
+
+    rng = np.random.default_rng(20241020)
+    cases = {}
+    for name in ("sparse", "dense"):
+        model = torch.zeros((n, n), dtype=torch.float64, device=dev)
+        if name == "sparse":
+            idx = torch.from_numpy(rng.choice(n * n, size=args.components, replace=False)).to(dev)
+            model.view(-1)[idx] = torch.from_numpy(rng.lognormal(0.0, 1.0, args.components)).to(dev)
+        else:
+            o, m = n // 2 - args.patch // 2, args.patch
+            model[o:o + m, o:o + m] = torch.randn((m, m), dtype=torch.float64, device=dev, generator=g)
+        row = {"nonzero": int(torch.count_nonzero(model))}
+        row["restore_ms"] = round(best(lambda: rst.device_restore(model, residual, beam, radius=radius, out=out)), 4)
+        inplace = residual.clone()
+        row["restore_inplace_ms"] = round(
+            best(lambda: rst.device_restore(model, inplace, beam, radius=radius, inplace=True)), 4)
+        del inplace
+        first = out.clone()
+        rst.device_restore(model, residual, beam, radius=radius, out=out)
+        row["identical_bits_on_repeat"] = bool(torch.equal(first.view(torch.int64), out.view(torch.int64)))
+        other = torch.empty_like(out)
+        for what, fn in (("torch_conv2d", torch_conv), ("torch_fft2", torch_fft)):
+            try:
+                row[what + "_ms"] = round(best(lambda: fn(model, other)), 3)
+                row[what + "_max_abs_diff"] = float((other - first).abs().max())
+                # away from the border: the fft2 form is circular, it wraps components near an edge around
+                row[what + "_max_abs_diff_interior"] = float(
+                    (other - first)[radius:n - radius, radius:n - radius].abs().max())
+                row["speedup_over_" + what] = round(row[what + "_ms"] / row["restore_ms"], 2)
+            except RuntimeError as exc:  # e.g. no fp64 convolution on this build
+                row[what + "_error"] = str(exc).splitlines()[0][:200]
+        del other, first, model
+        cases[name] = row
+    # the floor: the bytes a restore has to move (model and residual read, out written)
+    copy_ms = best(lambda: torch.add(residual, residual, out=out))
+    result = {"data": f"beam fitted to a 129^2 cut of device_ms2dirty(psf=True) on bench.py {args.config} inputs; "
+                      f"seeded {n}^2 residual; sparse: {args.components} seeded lognormal pixels; dense: a "
+                      f"{args.patch}^2 normal patch",
+              "npix": n, "beam": beam, "radius": radius, "taps": int(taps.numel()),
+              "metric": "ms per device_restore call (sparse model, fp64), best of repeats",
+              "value": cases["sparse"]["restore_ms"], "unit": "ms", "repeat": args.repeat,
+              "sparse": cases["sparse"], "dense": cases["dense"],
+              "torch_add_two_reads_one_write_ms": round(copy_ms, 4),
+              "GBs_at_24B_per_pixel_sparse": round(24.0 * n * n / cases["sparse"]["restore_ms"] / 1e6, 1)}
+    path = ROOT / "profiles" / f"restore_{args.config}.json"
+    path.write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "weights"), required=True)
-    ap.add_argument("--config", default="c3", help="weights: the bench.py configuration whose inputs are used")
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "weights", "restore"), required=True)
+    ap.add_argument("--config", default="c3", help="weights / restore: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--npix", type=int, default=2048)
@@ -294,6 +409,9 @@ def main():
     ap.add_argument("--gain", type=float, default=0.1, help="clean: loop gain")
     ap.add_argument("--sources", type=int, default=300, help="clean: point sources in the image")
     ap.add_argument("--batch", type=int, default=0, help="clean: iterations queued per readback (0: default)")
+    ap.add_argument("--restore-npix", type=int, default=8192, help="restore: image edge")
+    ap.add_argument("--components", type=int, default=10_000, help="restore: non-zero pixels of the sparse model")
+    ap.add_argument("--patch", type=int, default=512, help="restore: edge of the dense model patch")
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
 
@@ -306,6 +424,9 @@ def main():
         return
     if args.mode == "weights":
         print(json.dumps(weights(args)), flush=True)
+        return
+    if args.mode == "restore":
+        print(json.dumps(restore(args)), flush=True)
         return
     if args.mode == "clean":
         if args.psf_npix is None:
