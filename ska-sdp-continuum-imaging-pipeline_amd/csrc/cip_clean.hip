@@ -21,6 +21,7 @@
 // is bit-identical to the numpy statement res[win] -= f * psf[win'].
 #include <algorithm>
 
+#include "cip_clean_util.h"
 #include "cip_host.h"
 
 namespace cip {
@@ -34,73 +35,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kSelectThreads = 1024;
 constexpr int kSelectUnroll = 8;  // table entries one select thread loads before it compares
 static_assert(kTY == 128 && kTX % kWaves == 0, "a wave covers one tile row as 64 column pairs");
-
-struct Cand {
-  double a;     // |value|; -1: nothing selected yet
-  int64_t idx;  // flat index; INT64_MAX: none
-};
-
-__device__ __forceinline__ Cand cand_none() { return {-1.0, INT64_MAX}; }
-
-// `>` keeps NaN out (every comparison with it is false); ties go to the lower
-// flat index, so any reduction order gives the same winner
-__device__ __forceinline__ void cand_take(Cand& b, double a, int64_t idx) {
-  if (a > b.a || (a == b.a && idx < b.idx)) {
-    b.a = a;
-    b.idx = idx;
-  }
-}
-
-__device__ __forceinline__ Cand wave_best(Cand c) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double a = __shfl_down(c.a, off, 64);
-    const long long i = __shfl_down((long long)c.idx, off, 64);
-    cand_take(c, a, (int64_t)i);
-  }
-  return c;  // lane 0 holds the wave's best
-}
-
-// the workgroup's best in thread 0 (nwaves <= 16)
-template <int NWAVES>
-__device__ __forceinline__ Cand block_best(Cand c) {
-  __shared__ double s_a[NWAVES];
-  __shared__ long long s_i[NWAVES];
-  c = wave_best(c);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_a[wave] = c.a;
-    s_i[wave] = (long long)c.idx;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    Cand d = cand_none();
-    if (lane < NWAVES) {
-      d.a = s_a[lane];
-      d.idx = (int64_t)s_i[lane];
-    }
-    c = wave_best(d);
-  }
-  return c;
-}
-
-// one rounded multiply, one rounded subtract: contraction is off for this
-// expression (hipcc contracts a * b - c into an FMA by default)
-__device__ __forceinline__ double sub_rounded(double r, double f, double p) {
-#pragma clang fp contract(off)
-  const double prod = f * p;
-  return r - prod;
-}
-
-__device__ __forceinline__ double add_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 // One tile (tx, ty) by one workgroup: with SUB, res -= f * psf on the pixels
 // inside the PSF window around (pi, pj); then the tile's table entry over all

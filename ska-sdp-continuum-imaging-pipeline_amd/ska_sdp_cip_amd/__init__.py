@@ -9,7 +9,8 @@ Public API mirrors `/root/reference/src/ska_sdp_cip/__init__.py:1-10`
 built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), the
 clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_restore`), uniform and Briggs imaging weights (`weighting.py`,
-`cip_imaging_weights`) and the `uvw_tiling` package.
+`cip_imaging_weights`), multi-term multi-frequency synthesis (`mfs.py`,
+`cip_mfs_clean`) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -28,6 +29,16 @@ from .deconvolve import device_hogbom_clean, device_major_cycles, hogbom_clean  
 # it would hide the module of the same name
 from .restore import beam_from_fwhm, beam_taps, beam_to_sky, device_fit_beam, device_restore  # noqa: E402
 from .weighting import WeightDensity, device_imaging_weights, imaging_weights  # noqa: E402
+from . import mfs  # noqa: E402
+from .mfs import (  # noqa: E402
+    device_mfs_clean,
+    device_mfs_invert,
+    device_mfs_major_cycles,
+    device_mfs_residual,
+    mfs_clean,
+    mfs_hessian,
+    taylor_basis,
+)
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -72,4 +83,12 @@ __all__ = [
     "beam_from_fwhm",
     "beam_taps",
     "beam_to_sky",
+    "mfs",
+    "taylor_basis",
+    "mfs_hessian",
+    "mfs_clean",
+    "device_mfs_clean",
+    "device_mfs_invert",
+    "device_mfs_residual",
+    "device_mfs_major_cycles",
 ]

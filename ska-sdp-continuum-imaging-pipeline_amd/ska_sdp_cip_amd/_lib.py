@@ -1,5 +1,6 @@
 """
-ctypes binding of libcip_hip.so (C ABI: include/cip.h and include/cip_restore.h).
+ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h
+and include/cip_mfs.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -227,6 +228,13 @@ RESTORE_PROTOTYPES = {
     "cip_restore": (_i32, [_vp, _vp, _i64, _i64, _beam, _i64, _vp, _vp]),
 }
 
+# And for include/cip_mfs.h, the third (hinv is a HOST array).
+MFS_MAX_TERMS = 3  # CIP_MFS_MAX_TERMS
+MFS_PROTOTYPES = {
+    "cip_mfs_clean": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _pf64, _vp, _f64, _f64, _i64, _i64,
+                             _vp, _vp, _vp, _vp, ctypes.POINTER(CleanResult)]),
+}
+
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
@@ -241,7 +249,7 @@ def lib() -> ctypes.CDLL:
             "(make -C ska-sdp-continuum-imaging-pipeline_amd/csrc)"
         )
     so = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

@@ -21,6 +21,15 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     and the GB/s that implies at 24 B per window pixel, beside
                     the obvious torch loop on the same device (argmax(abs) ->
                     .item() -> sliced sub_) in the same run
+  --mode mfs_clean  device_mfs_clean (the joint minor cycle of multi-term MFS,
+                    --nterms Taylor terms) on seeded point sources with linear
+                    spectra convolved with the PSF stack of a real
+                    device_mfs_invert call, once with the full PSF and once
+                    with a --patch^2 cut: microseconds per iteration and the
+                    GB/s that implies at 8 (4T - 1) B per window pixel, beside
+                    device_hogbom_clean on term 0 at the same shapes and a
+                    torch loop that restates the operator, all in the same
+                    run; also written to profiles/mfs_clean_c3.json
   --mode weights    uniform imaging weights (weighting.py) on bench.py's C3
                     inputs and geometry: density / statistics / apply and the
                     one-shot call, best of --repeat; the synchronous
@@ -181,6 +190,130 @@ def clean(args):
             "batch": args.batch or _lib.CIP_CLEAN_DEFAULT_BATCH,
             "torch_loop_us_per_iteration": round(us_torch, 2), "speedup_over_torch_loop": round(us_torch / us, 2),
             "bit_identical_to_torch_loop": bool(torch.equal(res, res_t) and torch.equal(model, model_t))}
+
+
+def mfs_clean(args):
+    """us per iteration of device_mfs_clean, of device_hogbom_clean at the same shapes and of a torch loop."""
+    import torch
+
+    from ska_sdp_cip_amd import _lib, deconvolve, mfs, synthetic as syn
+
+    dev = torch.device("cuda", 0)
+    npix, nterms, gain, niter = args.npix, args.nterms, args.gain, args.niter
+    uvw_h = syn.uvw_tracks(args.rows, 64, array_radius_m=4000.0)
+    freq_h = syn.channel_frequencies(args.nchan)
+    px = syn.pixel_size_for_grid(uvw_h, freq_h, npix, support=8)
+    uvw, freq = torch.from_numpy(uvw_h).to(dev), torch.from_numpy(freq_h).to(dev)
+    ones = torch.ones((args.rows, args.nchan), dtype=torch.complex64, device=dev)
+    _, psf_full = mfs.device_mfs_invert(uvw, freq, ones, None, npix, px, nterms=nterms, support=8)
+    del ones
+    _lib.lib().cip_release_workspace()  # the invert's grid is not needed any more
+    hessian, hinv = mfs.mfs_hessian(psf_full)
+    hinv_d = torch.from_numpy(hinv).to(dev)
+    rng = np.random.default_rng(20241019)
+    where = (rng.integers(0, npix, args.sources), rng.integers(0, npix, args.sources))
+    fluxes = rng.lognormal(0.0, 1.0, args.sources)
+    slopes = rng.normal(-0.7, 0.3, args.sources) * fluxes
+
+    def case(pn):
+        o = npix // 2 - pn // 2  # the cut keeps the peak at (pn // 2, pn // 2)
+        psf = psf_full if pn == npix else psf_full[:, o:o + pn, o:o + pn].contiguous()
+        c = pn // 2
+
+        def window(i, j):
+            return max(0, i - c), min(npix, i - c + pn), max(0, j - c), min(npix, j - c + pn)
+
+        image = torch.zeros((nterms, npix, npix), dtype=torch.float64, device=dev)
+        for i, j, i0, i1 in zip(*where, fluxes, slopes):
+            a0, a1, b0, b1 = window(int(i), int(j))
+            cut = (slice(a0 - i + c, a1 - i + c), slice(b0 - j + c, b1 - j + c))
+            for t in range(nterms):
+                image[t, a0:a1, b0:b1] += float(i0) * psf[t][cut]
+                if nterms > 1:
+                    image[t, a0:a1, b0:b1] += float(i1) * psf[t + 1][cut]
+
+        def hip_run(n):
+            res = image.clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model, res, info = mfs.device_mfs_clean(res, psf, hinv, gain=gain, niter=n, inplace=True,
+                                                    return_components=True, batch=args.batch)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, model, res, info
+
+        def hogbom_run():
+            res = image[0].clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, _, info = deconvolve.device_hogbom_clean(res, psf[0], gain=gain, niter=niter, inplace=True,
+                                                        batch=args.batch)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, info
+
+        def torch_run(n):
+            res = image.clone()
+            model = torch.zeros_like(res)
+            flat_res, flat_model = res.view(nterms, -1), model.view(nterms, -1)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                s = hinv_d[0, 0] * res[0]
+                for t in range(1, nterms):
+                    s = s + hinv_d[0, t] * res[t]
+                flat = int(torch.argmax(torch.abs(s)).item())
+                r = flat_res[:, flat].clone()
+                f = []
+                for q in range(nterms):
+                    cq = hinv_d[q, 0] * r[0]
+                    for t in range(1, nterms):
+                        cq = cq + hinv_d[q, t] * r[t]
+                    f.append(gain * cq)
+                    flat_model[q, flat] += f[q]
+                a0, a1, b0, b1 = window(*divmod(flat, npix))
+                i, j = divmod(flat, npix)
+                cut = (slice(a0 - i + c, a1 - i + c), slice(b0 - j + c, b1 - j + c))
+                for t in range(nterms):
+                    for q in range(nterms):
+                        res[t, a0:a1, b0:b1].sub_(f[q] * psf[t + q][cut])
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, model, res
+
+        hip_run(min(niter, 8))  # warm-up: workspace, kernels
+        dt, _, _, info = min((hip_run(niter) for _ in range(args.repeat)), key=lambda r: r[0])
+        n = info["niter_done"]
+        pixels = 0
+        for flat in info["comp_index"].cpu().tolist():
+            a0, a1, b0, b1 = window(*divmod(flat, npix))
+            pixels += (a1 - a0) * (b1 - b0)
+        hogbom_run()
+        dt_h, info_h = min((hogbom_run() for _ in range(args.repeat)), key=lambda r: r[0])
+        nt = min(niter, args.torch_niter)
+        _, model, res, _ = hip_run(nt)
+        torch_run(2)
+        dt_t, model_t, res_t = torch_run(nt)
+        us, us_h, us_t = dt / n * 1e6, dt_h / info_h["niter_done"] * 1e6, dt_t / nt * 1e6
+        per_pixel = 8 * (4 * nterms - 1)
+        return {"psf_npix": pn, "niter": n, "stop": info["stop"], "us_per_iteration": round(us, 2),
+                "window_pixels_mean": round(pixels / n), "bytes_per_window_pixel": per_pixel,
+                "GBs_at_model_bytes": round(per_pixel * pixels / dt / 1e9, 1),
+                "hogbom_us_per_iteration": round(us_h, 2), "hogbom_niter": info_h["niter_done"],
+                "ratio_to_hogbom": round(us / us_h, 2), "byte_model_ratio": round((4 * nterms - 1) / 3, 2),
+                "torch_loop_us_per_iteration": round(us_t, 2), "torch_loop_niter": nt,
+                "speedup_over_torch_loop": round(us_t / us, 2),
+                "bit_identical_to_torch_loop": bool(torch.equal(res, res_t) and torch.equal(model, model_t))}
+
+    result = {"data": "synthetic (lognormal point sources with linear spectra convolved with the PSF stack of "
+                      "device_mfs_invert on real uvw tracks)",
+              "npix": npix, "nterms": nterms, "sources": args.sources, "gain": gain, "rows": args.rows,
+              "channels": args.nchan, "hessian": hessian.tolist(), "batch": args.batch or _lib.CIP_CLEAN_DEFAULT_BATCH,
+              "repeat": args.repeat, "metric": "us per iteration (device_mfs_clean, full PSF, fp64)",
+              "unit": "us/iteration"}
+    result["full_psf"] = case(npix)
+    result["patch"] = case(min(args.patch, npix))
+    result["value"] = result["full_psf"]["us_per_iteration"]
+    if npix == 8192 and nterms == 2:  # the row DESIGN.md 15 quotes
+        (ROOT / "profiles" / "mfs_clean_c3.json").write_text(json.dumps(result, indent=1) + "\n")
+    return result
 
 
 def weights(args):
@@ -390,7 +523,7 @@ def restore(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "weights", "restore"), required=True)
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "weights", "restore"), required=True)
     ap.add_argument("--config", default="c3", help="weights / restore: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
@@ -409,9 +542,12 @@ def main():
     ap.add_argument("--gain", type=float, default=0.1, help="clean: loop gain")
     ap.add_argument("--sources", type=int, default=300, help="clean: point sources in the image")
     ap.add_argument("--batch", type=int, default=0, help="clean: iterations queued per readback (0: default)")
+    ap.add_argument("--nterms", type=int, default=2, help="mfs_clean: Taylor terms")
+    ap.add_argument("--torch-niter", type=int, default=100, help="mfs_clean: iterations of the torch loop")
     ap.add_argument("--restore-npix", type=int, default=8192, help="restore: image edge")
     ap.add_argument("--components", type=int, default=10_000, help="restore: non-zero pixels of the sparse model")
-    ap.add_argument("--patch", type=int, default=512, help="restore: edge of the dense model patch")
+    ap.add_argument("--patch", type=int, default=512,
+                    help="restore: edge of the dense model patch; mfs_clean: edge of the PSF patch")
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
 
@@ -427,6 +563,9 @@ def main():
         return
     if args.mode == "restore":
         print(json.dumps(restore(args)), flush=True)
+        return
+    if args.mode == "mfs_clean":
+        print(json.dumps(mfs_clean(args)), flush=True)
         return
     if args.mode == "clean":
         if args.psf_npix is None:
