@@ -10,7 +10,8 @@ built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), the
 clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_restore`), uniform and Briggs imaging weights (`weighting.py`,
 `cip_imaging_weights`), multi-term multi-frequency synthesis (`mfs.py`,
-`cip_mfs_clean`) and the `uvw_tiling` package.
+`cip_mfs_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`)
+and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -38,6 +39,18 @@ from .mfs import (  # noqa: E402
     mfs_clean,
     mfs_hessian,
     taylor_basis,
+)
+from . import calibrate  # noqa: E402
+from .calibrate import (  # noqa: E402
+    GainCorrelator,
+    device_gain_apply,
+    device_gain_correlate,
+    device_gain_solve,
+    device_gaincal,
+    device_selfcal,
+    gain_apply,
+    gaincal,
+    solution_intervals,
 )
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
@@ -91,4 +104,14 @@ __all__ = [
     "device_mfs_invert",
     "device_mfs_residual",
     "device_mfs_major_cycles",
+    "calibrate",
+    "solution_intervals",
+    "GainCorrelator",
+    "device_gain_correlate",
+    "device_gain_solve",
+    "device_gain_apply",
+    "device_gaincal",
+    "device_selfcal",
+    "gaincal",
+    "gain_apply",
 ]

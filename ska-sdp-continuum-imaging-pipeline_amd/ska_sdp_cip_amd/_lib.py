@@ -1,6 +1,6 @@
 """
-ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h
-and include/cip_mfs.h).
+ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h,
+include/cip_mfs.h and include/cip_cal.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -236,6 +236,73 @@ MFS_PROTOTYPES = {
 }
 
 
+class CalScale(ctypes.Structure):
+    """Mirror of `cip_cal_scale` (include/cip_cal.h)."""
+
+    _fields_ = [
+        ("n_ant", ctypes.c_int64),
+        ("n_int", ctypes.c_int64),
+        ("amax", ctypes.c_double),
+        ("wmax", ctypes.c_double),
+        ("quantum", ctypes.c_double),
+        ("shift", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    @property
+    def corr_shape(self) -> tuple:
+        """Shape of the int64 correlation array: (n_int, n_ant, n_ant, 3)."""
+        return (self.n_int, self.n_ant, self.n_ant, 3)
+
+
+class CalCounts(ctypes.Structure):
+    """Mirror of `cip_cal_counts` (include/cip_cal.h)."""
+
+    _fields_ = [(name, ctypes.c_int64) for name in ("n_added", "n_zero", "n_outside", "n_bad")]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class CalSolveInfo(ctypes.Structure):
+    """Mirror of `cip_cal_solve_info` (include/cip_cal.h)."""
+
+    _fields_ = [
+        ("n_converged", ctypes.c_int64),
+        ("n_dead", ctypes.c_int64),
+        ("max_iter_done", ctypes.c_int64),
+        ("ref_missing", ctypes.c_int64),
+        ("max_change", ctypes.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# And for include/cip_cal.h, the fourth (the structs are HOST memory).
+# (named without the CIP_ prefix, which is kept for the codes of cip.h)
+CAL_MAX_ANT = 1024  # CIP_CAL_MAX_ANT
+CAL_CORRECT = 0  # CIP_CAL_CORRECT
+CAL_CORRUPT = 1  # CIP_CAL_CORRUPT
+CAL_PHASE_ONLY = 1  # CIP_CAL_PHASE_ONLY (a flag)
+CAL_MODES = {"correct": CAL_CORRECT, "corrupt": CAL_CORRUPT}
+_scale = ctypes.POINTER(CalScale)
+_counts = ctypes.POINTER(CalCounts)
+_sinfo = ctypes.POINTER(CalSolveInfo)
+_CAL_COLS = [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]  # vis .. wgt_dtype, nrow, nchan, ant1 ..
+CAL_PROTOTYPES = {
+    "cip_cal_scale_init": (_i32, [_i64, _i64, _f64, _f64, _i64, _scale]),
+    "cip_cal_correlate": (_i32, [*_CAL_COLS, _scale, _vp, _vp, _counts]),
+    "cip_cal_solve": (_i32, [_vp, _scale, _i64, _f64, _i64, _i32, _vp, _vp, _vp, _vp, _sinfo]),
+    "cip_cal_apply": (_i32, [_vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp,
+                             _vp]),
+    "cip_gaincal": (_i32, [*_CAL_COLS, _i64, _i64, _i64, _f64, _i64, _i32, _vp, _vp, _vp, _vp, _scale, _counts,
+                           _sinfo]),
+}
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
     global _LIB  # pylint: disable=global-statement
@@ -249,7 +316,8 @@ def lib() -> ctypes.CDLL:
             "(make -C ska-sdp-continuum-imaging-pipeline_amd/csrc)"
         )
     so = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items()):
+    for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items(),
+                                      *CAL_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so
@@ -285,6 +353,14 @@ def weight_grid(npix_x: int, npix_y: int, pixsize_x: float, pixsize_y: float, wm
     out = WeightGrid()
     check(lib().cip_weight_grid_init(int(npix_x), int(npix_y), float(pixsize_x), float(pixsize_y), float(wmax),
                                      int(nvis_max), ctypes.byref(out)))
+    return out
+
+
+def cal_scale(n_ant: int, n_int: int, amax: float, wmax: float, nsamp_max: int) -> CalScale:
+    """The fixed-point scale of `cip_cal_scale_init` (host-only)."""
+    out = CalScale()
+    check(lib().cip_cal_scale_init(int(n_ant), int(n_int), float(amax), float(wmax), int(nsamp_max),
+                                   ctypes.byref(out)))
     return out
 
 

@@ -86,6 +86,31 @@ def uvw_tracks(
     return np.ascontiguousarray(uvw, dtype=np.float64)
 
 
+def baseline_indices(n_rows: int, n_ant: int = 64):
+    """
+    (ant1, ant2, time_index) of `uvw_tracks`' rows, int32 each: the baselines
+    of `np.triu_indices(n_ant, 1)` (ant1 < ant2; row r's uvw is that of
+    enu[ant2] - enu[ant1]) tiled over the dumps, the last dump truncated to
+    give exactly `n_rows` rows.
+    """
+    a1, a2 = np.triu_indices(n_ant, k=1)
+    nbl = len(a1)
+    n_times = -(-n_rows // nbl)
+    time_index = np.repeat(np.arange(n_times), nbl)[:n_rows]
+    return (np.tile(a1, n_times)[:n_rows].astype(np.int32), np.tile(a2, n_times)[:n_rows].astype(np.int32),
+            time_index.astype(np.int32))
+
+
+def random_gains(n_int: int, n_ant: int, amp: float, phase: float, rng) -> NDArray:
+    """
+    Antenna gains, complex128 (n_int, n_ant): amplitudes U(1 - amp, 1 + amp)
+    and phases U(-phase, phase) radians, drawn independently per interval.
+    """
+    a = rng.uniform(1.0 - amp, 1.0 + amp, size=(n_int, n_ant))
+    ph = rng.uniform(-phase, phase, size=(n_int, n_ant))
+    return (a * np.exp(1j * ph)).astype(np.complex128)
+
+
 def channel_frequencies(
     nchan: int, f0: float = 856.0e6, bandwidth: Optional[float] = None
 ) -> NDArray:

@@ -45,6 +45,15 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     torch conv2d in fp64 with the same taps plus the add and a
                     torch fft2 convolution on the same device in the same run;
                     also written to profiles/restore_c3.json
+  --mode gaincal    gain calibration (calibrate.py) on bench.py's C3 inputs as
+                    the model column, the data being that column with seeded
+                    gains multiplied in, 64 antennas, intervals of 16 dumps:
+                    correlate / solve (50 iterations) / apply and the one-shot
+                    call, best of --repeat; a torch restatement of the
+                    correlate (fp64 terms, index_add_) and a read-only torch
+                    stream of the same 20 B per sample in the same run; the
+                    same for the samples laid out as rows of 64 channels; also
+                    written to profiles/gaincal_c3.json
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -413,6 +422,126 @@ def weights(args):
             "apply_GBs_at_8B_per_vis": round(8.0 * nvis / ms_apply / 1e6, 1)}
 
 
+def gaincal(args):
+    """ms of the gain-calibration calls, of a torch restatement of the correlate and of a read-only stream of the
+    same bytes, all on C3's inputs."""
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench  # the flagship workload's own inputs
+
+    from ska_sdp_cip_amd import calibrate
+    from ska_sdp_cip_amd import synthetic as syn
+
+    dev = torch.device("cuda", 0)
+    cfg = bench.CONFIGS[args.config]
+    result = _gaincal_case(args, cfg, bench, calibrate, syn, dev)
+    if cfg["nchan"] != 64:  # the same samples as rows of 64 channels: 16 lanes per row, four rows per wave
+        torch.cuda.empty_cache()
+        narrow = dict(cfg, rows=cfg["rows"] * cfg["nchan"] // 64, nchan=64)
+        result["rows_of_64_channels"] = _gaincal_case(args, narrow, bench, calibrate, syn, dev)
+    if args.config == "c3":  # the rows DESIGN.md 16 quotes
+        (ROOT / "profiles" / "gaincal_c3.json").write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
+
+def _gaincal_case(args, cfg, bench, calibrate, syn, dev):
+    """One shape of `gaincal`."""
+    import torch
+
+    _, _, model, wgt, _, _, _ = bench.make_inputs(cfg, 0, 1, dev)
+    nrow, nchan, n_ant, dumps = cfg["rows"], cfg["nchan"], 64, 16
+    nvis = nrow * nchan
+    a1, a2, t = (torch.from_numpy(a).to(dev) for a in syn.baseline_indices(nrow, n_ant))
+    interval = calibrate.solution_intervals(t, dumps)
+    n_int = int(interval.max()) + 1
+    truth = torch.from_numpy(syn.random_gains(n_int, n_ant, 0.2, 0.6, np.random.default_rng(1))).to(dev)
+    alive = torch.ones((n_int, n_ant), dtype=torch.uint8, device=dev)
+    # the data: the model column with the gains multiplied in
+    vis, _ = calibrate.device_gain_apply(model, None, a1, a2, interval, truth, alive, mode="corrupt")
+    cols = (a1, a2, interval)
+
+    def best(fn):
+        fn()  # warm-up: workspace buffers
+        times = []
+        for _ in range(args.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return min(times) * 1e3
+
+    amax = float(max(torch.view_as_real(vis).abs().max(), torch.view_as_real(model).abs().max()))
+    gc = calibrate.GainCorrelator(n_ant, n_int, amax, float(wgt.max()), nvis, dev)
+    counts = {}
+
+    def correlate():
+        gc.corr.zero_()
+        counts.update(gc.add_ms(vis, model, wgt, *cols))
+
+    ms_correlate = best(correlate)
+    solved = {}
+
+    def solve():
+        solved["out"] = gc.solve(niter=50, tol=0.0, refant=0)  # tol 0: all 50 iterations
+
+    ms_solve = best(solve)
+    gains, ok, _, _ = gc.solve(niter=50, tol=1e-8, refant=0)
+    out_vis, out_wgt = torch.empty_like(vis), torch.empty_like(wgt)
+    ms_apply = best(lambda: calibrate.device_gain_apply(vis, wgt, *cols, gains, ok, out=out_vis, wgt_out=out_wgt))
+    info = {}
+
+    def one_shot():
+        info.update(calibrate.device_gaincal(vis, model, wgt, *cols, n_ant, n_int, niter=50, tol=1e-8, refant=0)[2])
+
+    ms_total = best(one_shot)
+    keep = {}
+
+    def torch_run():
+        key = (interval.to(torch.int64) * n_ant + a1) * n_ant + a2
+        w64 = wgt.to(torch.float64)
+        m128 = model.to(torch.complex128)
+        c = (w64 * (vis.to(torch.complex128) * m128.conj())).sum(1)
+        m2 = (w64 * (m128.real * m128.real + m128.imag * m128.imag)).sum(1)
+        acc = torch.zeros((n_int * n_ant * n_ant, 3), dtype=torch.float64, device=dev)
+        acc.index_add_(0, key, torch.stack([c.real, c.imag, m2], 1))
+        keep["corr"] = acc.view(n_int, n_ant, n_ant, 3)
+
+    ms_torch = best(torch_run)
+    keep["sums"] = None
+
+    def stream():  # reads the same 20 bytes per sample and nothing else
+        keep["sums"] = (torch.view_as_real(vis).sum(), torch.view_as_real(model).sum(), wgt.sum())
+
+    ms_stream = best(stream)
+    mine = gc.corr.to(torch.float64) * gc.scale.quantum
+    rel = float((mine - keep["corr"]).abs().max() / keep["corr"].abs().max())
+    ref = truth * (truth[:, :1].conj() / truth[:, :1].abs())
+    err = float((gains - ref).abs().max())
+    bytes_per = 20.0
+    result = {"data": f"bench.py {args.config} inputs (complex64 model column with seeded gains multiplied in, "
+                      "float32 weights, 5% zero), baseline_indices of 64 antennas, intervals of 16 dumps",
+              "rows": nrow, "channels": nchan, "visibilities": nvis, "n_ant": n_ant, "n_int": n_int,
+              "metric": "ms per gain-calibration step, best of repeats", "value": round(ms_total, 3), "unit": "ms",
+              "repeat": args.repeat, "correlate_ms": round(ms_correlate, 3), "solve_50_iterations_ms": round(ms_solve, 3),
+              "apply_ms": round(ms_apply, 3), "one_shot_total_ms": round(ms_total, 3),
+              "one_shot_iterations": int(info["max_iter_done"]),
+              "torch_restatement_ms": round(ms_torch, 3),
+              "torch_restatement": "fp64 w v conj(m) and w |m|^2, row sums, index_add_ into (n_int n_ant^2, 3)",
+              "one_shot_speedup_over_torch_correlate": round(ms_torch / ms_total, 2),
+              "correlate_speedup_over_torch": round(ms_torch / ms_correlate, 2),
+              "torch_max_rel_diff": rel, "read_stream_ms": round(ms_stream, 3),
+              "read_stream": "torch sums of vis, model and wgt: the same 20 bytes per sample",
+              "correlate_GBs_at_20B_per_vis": round(bytes_per * nvis / ms_correlate / 1e6, 1),
+              "read_stream_GBs": round(bytes_per * nvis / ms_stream / 1e6, 1),
+              "apply_GBs_at_24B_per_vis": round(24.0 * nvis / ms_apply / 1e6, 1),
+              "correlate_atomics": 3 * nrow, "n_added": counts["n_added"], "n_zero": counts["n_zero"],
+              "n_outside": counts["n_outside"], "n_bad": counts["n_bad"], "shift": int(gc.scale.shift),
+              "max_gain_error": err}
+    return result
+
+
 def restore(args):
     """ms per device_restore call (sparse and dense model) and per torch conv2d / fft2 restatement."""
     import torch
@@ -523,8 +652,9 @@ def restore(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "weights", "restore"), required=True)
-    ap.add_argument("--config", default="c3", help="weights / restore: the bench.py configuration whose inputs are used")
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "weights", "restore",
+                                      "gaincal"), required=True)
+    ap.add_argument("--config", default="c3", help="weights / restore / gaincal: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--npix", type=int, default=2048)
@@ -563,6 +693,9 @@ def main():
         return
     if args.mode == "restore":
         print(json.dumps(restore(args)), flush=True)
+        return
+    if args.mode == "gaincal":
+        print(json.dumps(gaincal(args)), flush=True)
         return
     if args.mode == "mfs_clean":
         print(json.dumps(mfs_clean(args)), flush=True)
