@@ -21,8 +21,8 @@
 #include <cstring>
 
 #include "cip_cal.h"
-#include "cip_clean_util.h"
 #include "cip_host.h"
+#include "cip_rounded.h"
 
 // every kernel below is defined to the bit: no a * b + c becomes an FMA
 #pragma clang fp contract(off)

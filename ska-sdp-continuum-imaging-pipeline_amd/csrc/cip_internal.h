@@ -228,7 +228,7 @@ hipError_t launch_degrid_image(const double* dirty, int64_t npix_x, int64_t npix
 hipError_t launch_degrid_pad(const double* image, int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y,
                              const GridGeometry& g, double w_first, int np, double* planes, hipStream_t s);
 
-// ---- Hogbom CLEAN (cip_clean.hip) -----------------------------
+// ---- CLEAN minor cycle (cip_clean.hip) ------------------
 // image tiles of kCleanTileX rows x kCleanTileY columns (row segments contiguous)
 constexpr int kCleanTileX = 32;
 constexpr int kCleanTileY = 128;
@@ -238,28 +238,7 @@ struct alignas(16) CleanEntry {
   double absmax;
   int64_t index;
 };
-// device state of one cip_hogbom_clean call: the select kernel writes it, the
-// subtract kernel reads the peak and f, the host reads it back once per batch
-struct CleanState {
-  int64_t k;           // components written so far
-  int64_t pi, pj;      // the peak the next subtract is centred on
-  double f;            // gain * peak of that component
-  int32_t stopped;     // nonzero: every queued kernel returns at once
-  int32_t reason;      // CIP_CLEAN_* once stopped
-  double peak;         // signed value at the stopping peak (0 if EMPTY)
-  int64_t peak_index;  // its flat index (-1 if EMPTY)
-};
 int64_t clean_tiles(int64_t nx, int64_t ny);
-// zeroes the state and builds the table from res under mask (may be NULL)
-hipError_t launch_clean_init(double* res, int64_t nx, int64_t ny, const uint8_t* mask, CleanEntry* table,
-                             CleanState* state, hipStream_t s);
-hipError_t launch_clean_subtract(double* res, int64_t nx, int64_t ny, const double* psf, int64_t px, int64_t py,
-                                 int64_t cx, int64_t cy, const uint8_t* mask, CleanEntry* table,
-                                 const CleanState* state, hipStream_t s);
-// model, comp_index / comp_flux may be NULL
-hipError_t launch_clean_select(const double* res, int64_t nx, int64_t ny, const CleanEntry* table, double gain,
-                               double threshold, int64_t niter, double* model, int64_t* comp_index, double* comp_flux,
-                               CleanState* state, hipStream_t s);
 
 // ---- pruned 2-D FFT (cip_fft.hip) -----------------------------------------
 // gT: the grid transposed (nv rows of nu cells); H: (nx / 8) x nv x 8 complex;

@@ -28,6 +28,7 @@
 
 #include "cip_host.h"
 #include "cip_restore.h"
+#include "cip_rounded.h"
 
 namespace cip {
 
@@ -44,16 +45,6 @@ constexpr int kHalf = (kTY + 2 * kMaxR) / 2;  // columns one wave compacts: half
 constexpr int kListCap = kBlockRows * 2 * kHalf;
 static_assert(kTY == 128 && kTX == 32 && kMaxR <= kTX, "a wave owns rows w, w + 16; a tile sees 3 x 3 model tiles");
 static_assert(kWaves == 2 * kBlockRows && kHalf <= 128, "one wave per half row of a block, two loads per lane");
-
-__device__ __forceinline__ double add_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 // word t: bit r set when row r of model tile t holds a value != 0 (NaN counts)
 __global__ __launch_bounds__(kThreads) void restore_mark_kernel(const double* __restrict__ model, int64_t nx,

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "cip_host.h"
+#include "cip_rounded.h"
 
 namespace cip {
 
@@ -55,11 +56,6 @@ __device__ __forceinline__ int64_t weight_cell(double su, double sv, double wi, 
   // a NaN fails every comparison and an infinity the <=; fy >= 0 holds after the fold
   if (!(fabs(fx) <= g.hx && fy >= 0.0 && fy <= g.hy)) return -1;
   return ((int64_t)fx + g.hxi) * g.ny + (int64_t)fy;
-}
-
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
 }
 
 __device__ __forceinline__ double briggs_denominator(double d, double f2) {

@@ -29,6 +29,116 @@ try:
 except ModuleNotFoundError:  # pragma: no cover - torch is in the image
     torch = None
 
+_PF64 = ctypes.POINTER(ctypes.c_double)
+
+
+def _device_clean(residual, psf, hinv, stack, *, gain, threshold, niter, mask, model, psf_centre, inplace,
+                  return_components, batch):
+    """The minor cycle behind `device_hogbom_clean` (`stack` False: 2-D images,
+    no `hinv`, `cip_hogbom_clean`) and `mfs.device_mfs_clean` (`stack` True:
+    stacks and the host matrix `hinv`, `cip_mfs_clean`)."""
+    require_gpu()
+    dev = residual.device
+    names, kind = (("residuals", "psfs"), "stack of 2-D images") if stack else (("residual", "psf"), "2-D image")
+    for name, img in zip(names, (residual, psf)):
+        if img.dim() != 2 + stack:
+            raise ValueError(f"{name} must be a float64 {kind}, got {img.dtype} {tuple(img.shape)}")
+        check_array(img, (torch.float64,), None, dev, name)
+    shape = tuple(residual.shape[-2:])
+    # what cip_mfs_clean takes and cip_hogbom_clean does not: nterms (the stacks' first axis too) and hinv
+    terms = matrix = ()
+    if stack:
+        nterms = int(residual.shape[0])
+        h = np.ascontiguousarray(hinv.detach().cpu().numpy() if torch.is_tensor(hinv) else hinv, dtype=np.float64)
+        if h.ndim != 2 or h.shape[0] != h.shape[1]:
+            raise ValueError(f"hinv must be a square (nterms, nterms) matrix, got {h.shape}")
+        # nterms itself (1 .. 3) and the entries of hinv are the library's to refuse
+        if h.shape[0] != nterms or int(psf.shape[0]) != 2 * nterms - 1:
+            raise ValueError(f"{nterms} residual terms need hinv ({nterms}, {nterms}) and {2 * nterms - 1} PSFs, got "
+                             f"hinv {h.shape} and {int(psf.shape[0])} PSFs")
+        terms, matrix = (nterms,), (h.ctypes.data_as(_PF64),)
+    if mask is not None:
+        check_array(mask, (torch.uint8, torch.bool), shape, dev, "mask")
+        mask = mask.view(torch.uint8)
+    if model is not None:
+        check_array(model, (torch.float64,), (*terms, *shape), dev, "model")
+    cx, cy = (-1, -1) if psf_centre is None else (int(psf_centre[0]), int(psf_centre[1]))
+    if psf_centre is not None and (cx < 0 or cy < 0):
+        raise ValueError("psf_centre must lie inside the PSF")
+    niter = int(niter)
+    res = residual if inplace else residual.clone()
+    if model is None:
+        model = torch.zeros((*terms, *shape), dtype=torch.float64, device=dev)
+    comp_index = comp_flux = None
+    if return_components:
+        comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
+        comp_flux = torch.empty((max(niter, 1), *terms), dtype=torch.float64, device=dev)
+    result = _lib.CleanResult()
+    call(dev, "cip_mfs_clean" if stack else "cip_hogbom_clean", res, *terms, shape[0], shape[1], psf,
+         int(psf.shape[-2]), int(psf.shape[-1]), cx, cy, *matrix, mask, float(gain), float(threshold), niter,
+         int(batch), STREAM, model, comp_index, comp_flux, ctypes.byref(result))
+    info = {
+        "niter_done": int(result.niter_done),
+        "stop_reason": int(result.stop_reason),
+        "stop": _lib.CLEAN_STOP_REASONS[int(result.stop_reason)],
+        "peak": float(result.peak),
+        "peak_index": int(result.peak_index),
+    }
+    if return_components:
+        info["comp_index"] = comp_index[: info["niter_done"]]
+        info["comp_flux"] = comp_flux[: info["niter_done"]]
+    return model, res, info
+
+
+def _host_clean(device_clean, residual, psf, *hinv, mask, model, return_components, device, **kw):
+    """`hogbom_clean` and `mfs.mfs_clean`: `device_clean` on copies of host or
+    device arrays, numpy in -> numpy out."""
+    require_gpu()
+    dev = target_device(device)
+    numpy_in = isinstance(residual, np.ndarray)
+    with torch.cuda.device(dev):
+        res_d = to_device(residual, torch.float64, dev)
+        psf_d = to_device(psf, torch.float64, dev)
+        mask_d = None
+        if mask is not None:
+            m = np.asarray(mask) if not torch.is_tensor(mask) else mask
+            mask_d = to_device(m != 0, torch.bool, dev)
+        model_d = None if model is None else to_device(model, torch.float64, dev).clone()
+        model_d, res_d, info = device_clean(res_d, psf_d, *hinv, mask=mask_d, model=model_d, inplace=False,
+                                            return_components=return_components, **kw)
+        if numpy_in:
+            model_d, res_d = model_d.cpu().numpy(), res_d.cpu().numpy()
+            if return_components:
+                info["comp_index"] = info["comp_index"].cpu().numpy()
+                info["comp_flux"] = info["comp_flux"].cpu().numpy()
+    return model_d, res_d, info
+
+
+def _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, restore):
+    """The cycle loop of `device_major_cycles` and `mfs.device_mfs_major_cycles`.
+    `clean(threshold, probe)` returns the minor cycle's info (`probe`: niter=0,
+    the peak under the mask with nothing changed), `reinvert()` replaces the
+    residual by the re-inverted one, `restore(result)` (or None) adds the
+    restored images. Adds `peaks`, `components` and `stop_reason` to `result`."""
+    peaks, components = [], []
+    stop_reason = "n_major"
+    for _cycle in range(int(n_major)):
+        start = clean(threshold, True)
+        if start["stop_reason"] == _lib.CIP_CLEAN_EMPTY:
+            stop_reason = "empty"
+            break
+        peak = abs(start["peak"])
+        if peak <= threshold:
+            stop_reason = "threshold"
+            break
+        peaks.append(peak)
+        components.append(clean(max(threshold, cycle_fraction * peak), False)["niter_done"])
+        reinvert()
+    result.update(peaks=peaks, components=components, stop_reason=stop_reason)
+    if restore is not None:
+        restore(result)
+    return result
+
 
 def device_hogbom_clean(
     residual: "torch.Tensor",
@@ -61,42 +171,9 @@ def device_hogbom_clean(
     readbacks of the device state (0: library default); the result does not
     depend on it.
     """
-    require_gpu()
-    dev, shape = residual.device, tuple(residual.shape)
-    for name, img in (("residual", residual), ("psf", psf)):
-        if img.dim() != 2:
-            raise ValueError(f"{name} must be a float64 2-D image, got {img.dtype} {tuple(img.shape)}")
-        check_array(img, (torch.float64,), None, dev, name)
-    if mask is not None:
-        check_array(mask, (torch.uint8, torch.bool), shape, dev, "mask")
-        mask = mask.view(torch.uint8)
-    if model is not None:
-        check_array(model, (torch.float64,), shape, dev, "model")
-    cx, cy = (-1, -1) if psf_centre is None else (int(psf_centre[0]), int(psf_centre[1]))
-    if psf_centre is not None and (cx < 0 or cy < 0):
-        raise ValueError("psf_centre must lie inside the PSF")
-    niter = int(niter)
-    res = residual if inplace else residual.clone()
-    if model is None:
-        model = torch.zeros(shape, dtype=torch.float64, device=dev)
-    comp_index = comp_flux = None
-    if return_components:
-        comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
-        comp_flux = torch.empty(max(niter, 1), dtype=torch.float64, device=dev)
-    result = _lib.CleanResult()
-    call(dev, "cip_hogbom_clean", res, shape[0], shape[1], psf, int(psf.shape[0]), int(psf.shape[1]), cx, cy, mask,
-         float(gain), float(threshold), niter, int(batch), STREAM, model, comp_index, comp_flux, ctypes.byref(result))
-    info = {
-        "niter_done": int(result.niter_done),
-        "stop_reason": int(result.stop_reason),
-        "stop": _lib.CLEAN_STOP_REASONS[int(result.stop_reason)],
-        "peak": float(result.peak),
-        "peak_index": int(result.peak_index),
-    }
-    if return_components:
-        info["comp_index"] = comp_index[: info["niter_done"]]
-        info["comp_flux"] = comp_flux[: info["niter_done"]]
-    return model, res, info
+    return _device_clean(residual, psf, None, False, gain=gain, threshold=threshold, niter=niter, mask=mask,
+                         model=model, psf_centre=psf_centre, inplace=inplace, return_components=return_components,
+                         batch=batch)
 
 
 def hogbom_clean(
@@ -118,26 +195,9 @@ def hogbom_clean(
     torch in -> torch out (on the GPU). The inputs are never modified. Returns
     (model, residual, info) as `device_hogbom_clean`.
     """
-    require_gpu()
-    dev = target_device(device)
-    numpy_in = isinstance(residual, np.ndarray)
-    with torch.cuda.device(dev):
-        res_d = to_device(residual, torch.float64, dev)
-        psf_d = to_device(psf, torch.float64, dev)
-        mask_d = None
-        if mask is not None:
-            m = np.asarray(mask) if not torch.is_tensor(mask) else mask
-            mask_d = to_device(m != 0, torch.bool, dev)
-        model_d = None if model is None else to_device(model, torch.float64, dev).clone()
-        model_d, res_d, info = device_hogbom_clean(
-            res_d, psf_d, gain=gain, threshold=threshold, niter=niter, mask=mask_d, model=model_d,
-            psf_centre=psf_centre, inplace=False, return_components=return_components, batch=batch)
-        if numpy_in:
-            model_d, res_d = model_d.cpu().numpy(), res_d.cpu().numpy()
-            if return_components:
-                info["comp_index"] = info["comp_index"].cpu().numpy()
-                info["comp_flux"] = info["comp_flux"].cpu().numpy()
-    return model_d, res_d, info
+    return _host_clean(device_hogbom_clean, residual, psf, gain=gain, threshold=threshold, niter=niter, mask=mask,
+                       model=model, psf_centre=psf_centre, return_components=return_components, batch=batch,
+                       device=device)
 
 
 def device_major_cycles(
@@ -198,29 +258,19 @@ def device_major_cycles(
     residual, _ = device_ms2dirty(uvw, freq, vis, wgt, npix, npix, pixsize, pixsize, normalise=True,
                                   reuse_plan=True, **kw)
     model = torch.zeros((npix, npix), dtype=torch.float64, device=uvw.device)
-    peaks, components = [], []
-    stop_reason = "n_major"
-    for _cycle in range(int(n_major)):
-        # niter=0: the peak under the mask, nothing changed
-        _, _, start = device_hogbom_clean(residual, psf, gain=gain, threshold=threshold, niter=0, mask=mask,
-                                          inplace=True)
-        if start["stop_reason"] == _lib.CIP_CLEAN_EMPTY:
-            stop_reason = "empty"
-            break
-        peak = abs(start["peak"])
-        if peak <= threshold:
-            stop_reason = "threshold"
-            break
-        peaks.append(peak)
-        _, _, info = device_hogbom_clean(residual, psf, gain=gain, threshold=max(threshold, cycle_fraction * peak),
-                                         niter=niter, mask=mask, model=model, inplace=True)
-        components.append(info["niter_done"])
+
+    def clean(cycle_threshold, probe):
+        return device_hogbom_clean(residual, psf, gain=gain, threshold=cycle_threshold, niter=0 if probe else niter,
+                                   mask=mask, model=None if probe else model, inplace=True)[2]
+
+    def reinvert():
         vis_res = device_residual(uvw, freq, vis, model, pixsize, None, reuse_plan=True, **kw)
         device_ms2dirty(uvw, freq, vis_res, wgt, npix, npix, pixsize, pixsize, normalise=True, reuse_plan=True,
                         out=residual, **kw)
-    result = {"model": model, "residual": residual, "psf": psf, "peaks": peaks, "components": components,
-              "stop_reason": stop_reason}
-    if restore:
+
+    def add_restored(result):
         result["beam"] = device_fit_beam(psf) if beam is None else dict(beam)
         result["restored"] = device_restore(model, residual, result["beam"])
-    return result
+
+    return _major_cycles({"model": model, "residual": residual, "psf": psf}, n_major, threshold, cycle_fraction,
+                         clean, reinvert, add_restored if restore else None)

@@ -15,13 +15,13 @@ rounding included, in include/cip_mfs.h.
 
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from ._call import STREAM, call, check_array, check_rows, require_gpu, target_device, to_device
+from ._call import check_array, check_rows, require_gpu
+from .deconvolve import _device_clean, _host_clean, _major_cycles
 from .gridder import device_dirty2ms, device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .restore import device_fit_beam, device_restore
@@ -31,8 +31,6 @@ try:
     import torch
 except ModuleNotFoundError:  # pragma: no cover - torch is in the image
     torch = None
-
-_PF64 = ctypes.POINTER(ctypes.c_double)
 
 
 def _check_nterms(nterms) -> int:
@@ -118,51 +116,9 @@ def device_mfs_clean(
     (niter_done, T). T = 1 with hinv = [[1.0]] is `device_hogbom_clean` to
     the bit.
     """
-    require_gpu()
-    dev = residuals.device
-    for name, img in (("residuals", residuals), ("psfs", psfs)):
-        if img.dim() != 3:
-            raise ValueError(f"{name} must be a float64 stack of 2-D images, got {img.dtype} {tuple(img.shape)}")
-        check_array(img, (torch.float64,), None, dev, name)
-    nterms, shape = int(residuals.shape[0]), tuple(residuals.shape[1:])
-    h = np.ascontiguousarray(hinv.detach().cpu().numpy() if _is_tensor(hinv) else hinv, dtype=np.float64)
-    if h.ndim != 2 or h.shape[0] != h.shape[1]:
-        raise ValueError(f"hinv must be a square (nterms, nterms) matrix, got {h.shape}")
-    # nterms itself (1 .. 3) and the entries of hinv are the library's to refuse
-    if h.shape[0] != nterms or int(psfs.shape[0]) != 2 * nterms - 1:
-        raise ValueError(f"{nterms} residual terms need hinv ({nterms}, {nterms}) and {2 * nterms - 1} PSFs, got "
-                         f"hinv {h.shape} and {int(psfs.shape[0])} PSFs")
-    if mask is not None:
-        check_array(mask, (torch.uint8, torch.bool), shape, dev, "mask")
-        mask = mask.view(torch.uint8)
-    if model is not None:
-        check_array(model, (torch.float64,), (nterms, *shape), dev, "model")
-    cx, cy = (-1, -1) if psf_centre is None else (int(psf_centre[0]), int(psf_centre[1]))
-    if psf_centre is not None and (cx < 0 or cy < 0):
-        raise ValueError("psf_centre must lie inside the PSF")
-    niter = int(niter)
-    res = residuals if inplace else residuals.clone()
-    if model is None:
-        model = torch.zeros((nterms, *shape), dtype=torch.float64, device=dev)
-    comp_index = comp_flux = None
-    if return_components:
-        comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
-        comp_flux = torch.empty((max(niter, 1), max(nterms, 1)), dtype=torch.float64, device=dev)
-    result = _lib.CleanResult()
-    call(dev, "cip_mfs_clean", res, nterms, shape[0], shape[1], psfs, int(psfs.shape[1]), int(psfs.shape[2]), cx, cy,
-         h.ctypes.data_as(_PF64), mask, float(gain), float(threshold), niter, int(batch), STREAM, model, comp_index,
-         comp_flux, ctypes.byref(result))
-    info = {
-        "niter_done": int(result.niter_done),
-        "stop_reason": int(result.stop_reason),
-        "stop": _lib.CLEAN_STOP_REASONS[int(result.stop_reason)],
-        "peak": float(result.peak),
-        "peak_index": int(result.peak_index),
-    }
-    if return_components:
-        info["comp_index"] = comp_index[: info["niter_done"]]
-        info["comp_flux"] = comp_flux[: info["niter_done"]]
-    return model, res, info
+    return _device_clean(residuals, psfs, hinv, True, gain=gain, threshold=threshold, niter=niter, mask=mask,
+                         model=model, psf_centre=psf_centre, inplace=inplace, return_components=return_components,
+                         batch=batch)
 
 
 def mfs_clean(
@@ -185,26 +141,9 @@ def mfs_clean(
     in -> torch out (on the GPU). The inputs are never modified. Returns
     (model, residuals, info) as `device_mfs_clean`.
     """
-    require_gpu()
-    dev = target_device(device)
-    numpy_in = isinstance(residuals, np.ndarray)
-    with torch.cuda.device(dev):
-        res_d = to_device(residuals, torch.float64, dev)
-        psf_d = to_device(psfs, torch.float64, dev)
-        mask_d = None
-        if mask is not None:
-            m = np.asarray(mask) if not torch.is_tensor(mask) else mask
-            mask_d = to_device(m != 0, torch.bool, dev)
-        model_d = None if model is None else to_device(model, torch.float64, dev).clone()
-        model_d, res_d, info = device_mfs_clean(
-            res_d, psf_d, hinv, gain=gain, threshold=threshold, niter=niter, mask=mask_d, model=model_d,
-            psf_centre=psf_centre, inplace=False, return_components=return_components, batch=batch)
-        if numpy_in:
-            model_d, res_d = model_d.cpu().numpy(), res_d.cpu().numpy()
-            if return_components:
-                info["comp_index"] = info["comp_index"].cpu().numpy()
-                info["comp_flux"] = info["comp_flux"].cpu().numpy()
-    return model_d, res_d, info
+    return _host_clean(device_mfs_clean, residuals, psfs, hinv, gain=gain, threshold=threshold, niter=niter, mask=mask,
+                       model=model, psf_centre=psf_centre, return_components=return_components, batch=batch,
+                       device=device)
 
 
 def device_mfs_invert(
@@ -382,29 +321,18 @@ def device_mfs_major_cycles(
         hinv = np.ones((1, 1))
     models = torch.zeros_like(residuals)
     degrid = scratch if scratch.dtype == torch.complex128 else None
-    peaks, components = [], []
-    stop_reason = "n_major"
-    for _cycle in range(int(n_major)):
-        _, _, start = device_mfs_clean(residuals, psfs, hinv, gain=gain, threshold=threshold, niter=0, mask=mask,
-                                       inplace=True)
-        if start["stop_reason"] == _lib.CIP_CLEAN_EMPTY:
-            stop_reason = "empty"
-            break
-        peak = abs(start["peak"])
-        if peak <= threshold:
-            stop_reason = "threshold"
-            break
-        peaks.append(peak)
-        _, _, info = device_mfs_clean(residuals, psfs, hinv, gain=gain,
-                                      threshold=max(threshold, cycle_fraction * peak), niter=niter, mask=mask,
-                                      model=models, inplace=True)
-        components.append(info["niter_done"])
+
+    def clean(cycle_threshold, probe):
+        return device_mfs_clean(residuals, psfs, hinv, gain=gain, threshold=cycle_threshold,
+                                niter=0 if probe else niter, mask=mask, model=None if probe else models,
+                                inplace=True)[2]
+
+    def reinvert():
         vis_res = device_mfs_residual(uvw, freq, vis, models, pixsize, ref, reuse_plan=True, scratch=degrid, **kw)
         device_mfs_invert(uvw, freq, vis_res, wgt, npix, pixsize, nterms=nterms, ref_freq=ref, want_psfs=False,
                           reuse_plan=True, out=residuals, scratch=scratch, **kw)
-    result = {"models": models, "residuals": residuals, "psfs": psfs, "hessian": hessian, "hinv": hinv,
-              "ref_freq": ref, "peaks": peaks, "components": components, "stop_reason": stop_reason}
-    if restore:
+
+    def add_restored(result):
         result["beam"] = device_fit_beam(psfs[0]) if beam is None else dict(beam)
         solved = torch.einsum("tq,qij->tij", torch.from_numpy(hinv).to(residuals.device), residuals)
         result["restored"] = torch.stack([device_restore(models[t], solved[t].contiguous(), result["beam"])
@@ -413,4 +341,7 @@ def device_mfs_major_cycles(
             i0 = result["restored"][0]
             result["alpha"] = torch.where(i0.abs() > alpha_cut, result["restored"][1] / i0,
                                           torch.full_like(i0, float("nan")))
-    return result
+
+    result = {"models": models, "residuals": residuals, "psfs": psfs, "hessian": hessian, "hinv": hinv,
+              "ref_freq": ref}
+    return _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, add_restored if restore else None)

@@ -85,6 +85,32 @@ def test_degenerate_images(shape):
     _check(img, _psf(2 * shape[0], 2 * shape[1]), gain=0.3, niter=25)
 
 
+@pytest.mark.parametrize("ny", [300, 301], ids=["even-16B", "odd-8B"])
+def test_both_access_widths(ny):
+    # 70 x 300: 3 x 3 tiles of 32 x 128 pixels, partial on both axes; the odd width takes the 8-byte path
+    ref = _check(_image(70, ny, seed=6), _psf(70, 45), gain=0.2, niter=50)
+    assert ref[2]["niter_done"] == 50
+
+
+def test_base_misaligned_to_16_bytes():
+    import torch
+
+    img, psf = _image(70, 300, seed=6), _psf(70, 45)
+    ref_model, ref_res, ref_info = _clean_np.hogbom_clean(img, psf, gain=0.2, niter=50)
+    storage = torch.zeros(img.size + 1, dtype=torch.float64, device="cuda")
+    view = storage[1:].view(img.shape)  # starts one double into its storage: even width, 8-byte path
+    view.copy_(_t(img))
+    assert view.data_ptr() % 16 == 8 and view.is_contiguous()
+    model, res, info = deconvolve.device_hogbom_clean(view, _t(psf), gain=0.2, niter=50, inplace=True,
+                                                      return_components=True)
+    assert res is view and storage[0].item() == 0.0
+    assert info["niter_done"] == ref_info["niter_done"] == 50 and info["peak_index"] == ref_info["peak_index"]
+    assert _same(np.float64(info["peak"]), np.float64(ref_info["peak"]))
+    assert _same(info["comp_index"].cpu().numpy(), ref_info["comp_index"])
+    assert _same(info["comp_flux"].cpu().numpy(), ref_info["comp_flux"])
+    assert _same(res.cpu().numpy(), ref_res) and _same(model.cpu().numpy(), ref_model)
+
+
 @pytest.fixture(scope="module")
 def big():
     """1030 x 515 (33 x 5 tiles of 32 x 128 pixels, a partial tile on both axes)

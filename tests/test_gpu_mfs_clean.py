@@ -10,7 +10,8 @@ residuals, models, component indices and fluxes, `niter_done`, `stop_reason`,
 Images are seeded standard-normal noise with a few planted spikes, a different
 draw per Taylor term; PSF plane k is 0.5^k exp(-r^2 / 8) cos((0.7 + 0.1 k) r);
 hinv is a seeded symmetric positive-definite matrix whose off-diagonals are
-not zero, so the cross terms count.
+not zero, so the cross terms count. `cip_hogbom_clean` runs the T = 1 kernels,
+so the shape and selection cases take T = 1 too, with a hinv that is not 1.0.
 """
 
 import ctypes
@@ -96,6 +97,8 @@ def _first_record_low(info, candidates):
 
 # ------------------------------------------------------- T = 1 is Hogbom ----
 def test_one_term_identity_equals_hogbom():
+    # both entry points run the same T = 1 kernels: this guards the two wrappers
+    # (the Hogbom cases of test_gpu_clean.py against _clean_np are the check of the kernels)
     img, psf = _images(1, 70, 45), _psfs(1, 33, 21)
     h_model, h_res, h_info = deconvolve.device_hogbom_clean(_t(img[0]), _t(psf[0]), gain=0.2, niter=60,
                                                             return_components=True)
@@ -111,14 +114,14 @@ def test_one_term_identity_equals_hogbom():
 
 
 # ---------------------------------------------------------------- shapes ----
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 @pytest.mark.parametrize("pshape", [(33, 21), (70, 45), (140, 90)], ids=["patch", "equal", "covers"])
 def test_odd_image_against_psf_sizes(nterms, pshape):
     ref = _check(_images(nterms, 70, 45), _psfs(nterms, *pshape), _hinv(nterms), gain=0.2, niter=60)
     assert ref[2]["niter_done"] == 60 and ref[2]["stop_reason"] == _mfs_np.NITER
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 @pytest.mark.parametrize("ny", [300, 301], ids=["even-16B", "odd-8B"])
 def test_both_tile_edges_and_both_access_widths(nterms, ny):
     # 100 x 300: 4 x 3 tiles of 32 x 128 pixels, partial on both axes; the odd width takes the 8-byte path
@@ -126,7 +129,7 @@ def test_both_tile_edges_and_both_access_widths(nterms, ny):
     assert ref[2]["niter_done"] == 50
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 def test_base_misaligned_to_16_bytes(nterms):
     import torch
 
@@ -143,7 +146,7 @@ def test_base_misaligned_to_16_bytes(nterms):
     assert _same(res.cpu().numpy(), ref_res) and _same(model.cpu().numpy(), ref_model)
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 @pytest.mark.parametrize("shape", [(1, 1), (1, 300), (300, 1)])
 def test_degenerate_images(nterms, shape):
     img = np.random.default_rng(5).standard_normal((nterms, *shape))
@@ -151,7 +154,7 @@ def test_degenerate_images(nterms, shape):
     _check(img, _psfs(nterms, 2 * shape[0], 2 * shape[1]), _hinv(nterms), gain=0.3, niter=25)
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 @pytest.mark.parametrize("centre", [(0, 0), (5, 20)])
 def test_psf_centre_off_the_middle(nterms, centre):
     _check(_images(nterms, 70, 45), _psfs(nterms, 33, 21, centre), _hinv(nterms), gain=0.2, niter=40,
@@ -185,7 +188,7 @@ def test_more_tiles_than_one_select_round():
 
 
 # ------------------------------------------------------------- selection ----
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 def test_mask_excludes_the_global_peak(nterms):
     img, hinv = _images(nterms, 70, 45), _hinv(nterms)
     mask = (np.random.default_rng(2).random((70, 45)) < 0.5).astype(np.uint8)
@@ -204,7 +207,7 @@ def test_all_zero_mask_is_empty():
     assert _same(ref[1], img)
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 def test_nan_in_one_plane_only_is_never_chosen(nterms):
     img, hinv, psf = _images(nterms, 70, 45), _hinv(nterms), _psfs(nterms, 9, 9)
     would_be = _mfs_np.mfs_clean(img, psf, hinv, niter=0)[2]["peak_index"]
@@ -215,7 +218,7 @@ def test_nan_in_one_plane_only_is_never_chosen(nterms):
     _check(np.full((nterms, 70, 45), np.nan), psf, hinv, niter=5)  # nothing to select: EMPTY
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 def test_equal_maxima_take_the_lower_index(nterms):
     img, hinv = _images(nterms, 70, 45, spikes=False), _hinv(nterms)
     for t in range(nterms):  # the same T values at three pixels: the same s, far above the noise
@@ -233,7 +236,7 @@ def test_niter_zero_reports_the_peak():
     assert ref[2]["peak"] == hinv[0, 0] * img[0, i, j] + hinv[0, 1] * img[1, i, j]  # the signed s, not r_0
 
 
-@pytest.mark.parametrize("nterms", [2, 3])
+@pytest.mark.parametrize("nterms", [1, 2, 3])
 def test_threshold_hit_exactly(nterms):
     img, psf, hinv = _images(nterms, 70, 45), _psfs(nterms, 33, 21), _hinv(nterms)
     k = _first_record_low(_mfs_np.mfs_clean(img, psf, hinv, gain=0.2, niter=40)[2], range(10, 40))

@@ -2,7 +2,7 @@
 # Experiment builds of libcip_hip.so with ONE translation unit compiled with
 # extra flags: tools/build_variant_unit.sh <unit> <name> <flags...>, unit one
 # of workspace params planner invert predict plan grid tiling fft collective strips degrid
-# clean scatter_w<W>; output
+# clean (both minor cycles) weights restore cal scatter_w<W>; output
 # tools/variants/libcip_hip_<name>.so (select with CIP_HIP_LIB). Needs the
 # normal build first (its objects are reused for the other units).
 set -e
@@ -14,6 +14,7 @@ case $unit in scatter_w*) src=cip_scatter_w.hip; extra="-DCIP_SCATTER_W=${unit#s
   $extra "$@" -c $src -o build/variant_$name.o
 objs=""
 for u in workspace params planner invert predict plan grid tiling fft collective strips degrid clean \
+         weights restore cal \
          degrid_w4 degrid_w6 degrid_w8 degrid_w10 degrid_w12 degrid_w14 degrid_w16 \
          scatter_w4 scatter_w6 scatter_w8 scatter_w10 scatter_w12 scatter_w14 scatter_w16 \
          scatter_large_w24 scatter_large_w32 scatter_large_w48 scatter_large_w64; do
