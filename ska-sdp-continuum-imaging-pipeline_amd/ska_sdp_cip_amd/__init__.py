@@ -10,8 +10,8 @@ built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), the
 clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_restore`), uniform and Briggs imaging weights (`weighting.py`,
 `cip_imaging_weights`), multi-term multi-frequency synthesis (`mfs.py`,
-`cip_mfs_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`)
-and the `uvw_tiling` package.
+`cip_mfs_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`), the sky-model
+predict (`skymodel.py`, `cip_dft_predict`) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -52,6 +52,8 @@ from .calibrate import (  # noqa: E402
     gaincal,
     solution_intervals,
 )
+from . import skymodel  # noqa: E402
+from .skymodel import SkyModel, device_dft_predict, dft_predict  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -114,4 +116,8 @@ __all__ = [
     "device_selfcal",
     "gaincal",
     "gain_apply",
+    "skymodel",
+    "SkyModel",
+    "device_dft_predict",
+    "dft_predict",
 ]

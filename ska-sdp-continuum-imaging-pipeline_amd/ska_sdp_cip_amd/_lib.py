@@ -1,6 +1,6 @@
 """
 ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h,
-include/cip_mfs.h and include/cip_cal.h).
+include/cip_mfs.h, include/cip_cal.h and include/cip_dft.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -302,6 +302,16 @@ CAL_PROTOTYPES = {
                            _sinfo]),
 }
 
+# And for include/cip_dft.h, the fifth: the flags are a namespace of their own.
+DFT_ADD = 1  # CIP_DFT_ADD
+DFT_SUBTRACT = 2  # CIP_DFT_SUBTRACT
+DFT_WTERM = 4  # CIP_DFT_WTERM
+DFT_FAST = 8  # CIP_DFT_FAST
+DFT_MODES = {"set": 0, "add": DFT_ADD, "subtract": DFT_SUBTRACT}
+DFT_PROTOTYPES = {
+    "cip_dft_predict": (_i32, [*_ROWS, _vp, _vp, _vp, _i64, _i64, _f64, _i32, _vp, _i32, _vp, _vp, _i32]),
+}
+
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
@@ -317,7 +327,7 @@ def lib() -> ctypes.CDLL:
         )
     so = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items(),
-                                      *CAL_PROTOTYPES.items()):
+                                      *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

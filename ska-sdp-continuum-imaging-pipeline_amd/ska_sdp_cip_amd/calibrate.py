@@ -25,6 +25,7 @@ from ._call import (STREAM, VIS_DTYPES, WGT_DTYPES, call, check_array, require_g
 from .deconvolve import device_major_cycles
 from .gridder import device_dirty2ms
 from .invert import DO_WSTACKING, EPSILON
+from .skymodel import device_dft_predict
 
 try:
     import torch
@@ -290,7 +291,7 @@ def gain_apply(vis, wgt, ant1, ant2, interval, gains, ant_ok=None, *, mode="corr
 
 def device_selfcal(uvw, freq, vis, wgt, ant1, ant2, interval, npix: int, pixsize: float, *, n_rounds: int,
                    phase_only: bool = True, refant: int = 0, solver_niter: int = 50, solver_tol: float = 1e-8,
-                   **major_cycle_kwargs):
+                   initial_sky_model=None, **major_cycle_kwargs):
     """
     Self-calibration on device-resident data: `n_rounds` rounds of
 
@@ -312,6 +313,15 @@ def device_selfcal(uvw, freq, vis, wgt, ant1, ant2, interval, npix: int, pixsize
     number of antennas and intervals is taken from the largest index.
     Amplitude self-calibration (`phase_only=False`) leaves the flux scale free
     to drift; nothing here normalises it.
+
+    `initial_sky_model` (a `skymodel.SkyModel`, for instance a catalogue of
+    the field's bright sources): the loop does not start blind. Before the
+    first round, `device_dft_predict` of it (with the w term when
+    `do_wstacking`) fills the model column, `device_gaincal` solves the
+    ORIGINAL `vis` against it and `device_gain_apply` corrects the data, so
+    round 1 images calibrated visibilities. The dict then also holds
+    `initial_gains`, `initial_ant_ok` and `initial_solver`. With None the loop
+    is what it is without the argument.
     """
     require_gpu()
     n_rounds = int(n_rounds)
@@ -336,18 +346,25 @@ def device_selfcal(uvw, freq, vis, wgt, ant1, ant2, interval, npix: int, pixsize
         peaks.append(res["peaks"][0] if res["peaks"] else 0.0)
         rms.append(float(torch.sqrt(torch.mean(res["residual"] * res["residual"]))))
 
+    def solve_and_apply():
+        g, ok, info = device_gaincal(vis, model_col, wgt0, ant1, ant2, interval, n_ant, n_int, niter=solver_niter,
+                                     tol=solver_tol, refant=refant, phase_only=phase_only)
+        info.pop("iters")
+        return g, ok, info, device_gain_apply(vis, wgt0, ant1, ant2, interval, g, ok, mode="correct", out=buf_vis,
+                                              wgt_out=buf_wgt)
+
+    initial = {}
+    if initial_sky_model is not None:
+        device_dft_predict(uvw, freq, initial_sky_model, out=model_col, w_term=bool(predict_kw["do_wstacking"]))
+        g0, ok0, info0, (vis_c, wgt_c) = solve_and_apply()
+        initial = dict(initial_gains=g0, initial_ant_ok=ok0, initial_solver=info0)
     for _round in range(n_rounds):
         res = device_major_cycles(uvw, freq, vis_c, wgt_c, npix, pixsize, **major_cycle_kwargs)
         record(res)
         device_dirty2ms(uvw, freq, res["model"], None, pixsize, pixsize, out=model_col, reuse_plan=True, **predict_kw)
-        gains, ant_ok, info = device_gaincal(vis, model_col, wgt0, ant1, ant2, interval, n_ant, n_int,
-                                             niter=solver_niter, tol=solver_tol, refant=refant,
-                                             phase_only=phase_only)
-        info.pop("iters")
+        gains, ant_ok, info, (vis_c, wgt_c) = solve_and_apply()
         solver.append(info)
-        vis_c, wgt_c = device_gain_apply(vis, wgt0, ant1, ant2, interval, gains, ant_ok, mode="correct", out=buf_vis,
-                                         wgt_out=buf_wgt)
     res = device_major_cycles(uvw, freq, vis_c, wgt_c, npix, pixsize, **major_cycle_kwargs)
     record(res)
-    res.update(gains=gains, ant_ok=ant_ok, round_peaks=peaks, round_rms=rms, solver=solver)
+    res.update(gains=gains, ant_ok=ant_ok, round_peaks=peaks, round_rms=rms, solver=solver, **initial)
     return res

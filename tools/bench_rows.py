@@ -54,6 +54,15 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     stream of the same 20 B per sample in the same run; the
                     same for the samples laid out as rows of 64 channels; also
                     written to profiles/gaincal_c3.json
+  --mode dft        device_dft_predict (skymodel.py, the sky-model predict) on
+                    bench.py's C3 rows (390,625 x 256): 64 and 1024 seeded
+                    components, points and Gaussians, the fp64 and the fast
+                    class, complex64 output with weights, best of --repeat
+                    around a synchronised call: ms and (visibility, component)
+                    pairs per second, beside a torch restatement of the same
+                    sum in fp64 on the same device in the same run (64
+                    components: best of --repeat; 1024: one run); also written
+                    to profiles/dft_predict_c3.json
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -542,6 +551,102 @@ def _gaincal_case(args, cfg, bench, calibrate, syn, dev):
     return result
 
 
+def dft(args):
+    """ms per device_dft_predict call and per torch restatement of the same sum, on C3's rows."""
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench  # the flagship workload's own rows
+
+    from ska_sdp_cip_amd import skymodel
+
+    dev = torch.device("cuda", 0)
+    cfg = bench.CONFIGS[args.config]
+    uvw, freq, _, wgt, px, _, _ = bench.make_inputs(cfg, 0, 1, dev)
+    nrow, nchan = cfg["rows"], cfg["nchan"]
+    nvis = nrow * nchan
+    fx = freq / 299792458.0
+    out = torch.empty((nrow, nchan), dtype=torch.complex64, device=dev)
+
+    def best(fn, repeat):
+        times = []
+        for _ in range(repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return min(times) * 1e3
+
+    def sky_of(ncomp, gauss):
+        rng = np.random.default_rng(ncomp)
+        fov = cfg["npix"] * px  # inside the C3 image
+        lm = rng.uniform(-fov / 2, fov / 2, (ncomp, 2))
+        flux = rng.uniform(0.1, 1.0, (ncomp, 1))
+        shape = None
+        if gauss:
+            major = rng.uniform(2.0, 20.0, ncomp) * px
+            shape = torch.from_numpy(np.stack([major, major * rng.uniform(0.3, 1.0, ncomp),
+                                               rng.uniform(-np.pi, np.pi, ncomp)], axis=1))
+        return skymodel.SkyModel(torch.from_numpy(lm), torch.from_numpy(flux), shape=shape).to(dev)
+
+    def torch_run(sky, keep, chunk=16_384):  # the same sum in fp64: w term, envelope, weights, one rounding
+        l, m = sky.lm[:, 0], sky.lm[:, 1]  # noqa: E741
+        nm1 = -(l * l + m * m) / (torch.sqrt(1.0 - l * l - m * m) + 1.0)
+        res = torch.empty_like(out)
+        for a in range(0, nrow, chunk):
+            u, v, w = (uvw[a:a + chunk, k:k + 1] for k in range(3))
+            acc = torch.zeros((u.shape[0], nchan), dtype=torch.complex128, device=dev)
+            for k in range(len(sky)):
+                ph = (u * l[k] + v * m[k] - w * nm1[k]) * fx[None, :]
+                term = torch.polar(sky.flux[k, 0].expand_as(ph), (-2.0 * np.pi) * (ph - torch.round(ph)))
+                if sky.shape is not None:
+                    sp, cp = torch.sin(sky.shape[k, 2]), torch.cos(sky.shape[k, 2])
+                    q = 3.559707331246876 * ((sky.shape[k, 0] * (u * sp + v * cp)) ** 2
+                                              + (sky.shape[k, 1] * (u * cp - v * sp)) ** 2)
+                    term = term * torch.exp(-(fx * fx)[None, :] * q)
+                acc += term
+            res[a:a + chunk] = (wgt[a:a + chunk].to(torch.float64) * acc).to(torch.complex64)
+        keep["torch"] = res
+
+    cases = []
+    for ncomp in (64, 1024):
+        for gauss in (False, True):
+            sky = sky_of(ncomp, gauss)
+            row = {"ncomp": ncomp, "components": "gaussians" if gauss else "points", "pairs": nvis * ncomp}
+            sigma = float(sky.flux.abs().sum())
+            for name, fast in (("fp64", False), ("fast", True)):
+                run = lambda: skymodel.device_dft_predict(uvw, freq, sky, wgt, out=out, fast=fast)  # noqa: E731
+                run()  # warm-up: code object, workspace
+                ms = best(run, args.repeat)
+                row[f"{name}_ms"] = round(ms, 3)
+                row[f"{name}_pairs_per_s"] = float(f"{nvis * ncomp / ms * 1e3:.4g}")
+                row[f"{name}_column"] = out.clone() if name == "fp64" else None
+            keep = {}
+            if ncomp == 64:
+                torch_run(sky_of(2, gauss), keep)  # warm-up at two components
+            row["torch_fp64_ms"] = round(best(lambda: torch_run(sky, keep), args.repeat if ncomp == 64 else 1), 3)
+            row["torch_runs"] = args.repeat if ncomp == 64 else 1
+            row["fp64_speedup_over_torch"] = round(row["torch_fp64_ms"] / row["fp64_ms"], 1)
+            row["fast_speedup_over_torch"] = round(row["torch_fp64_ms"] / row["fast_ms"], 1)
+            row["fp64_vs_torch_max_diff_over_sigma"] = float((row.pop("fp64_column") - keep["torch"]).abs().max()) / sigma
+            row.pop("fast_column")
+            cases.append(row)
+            del keep
+            torch.cuda.empty_cache()
+    result = {"data": f"bench.py {args.config} rows and weights (float32, 5% zero), seeded components inside the "
+                      "image, one Taylor term, w term on, complex64 output",
+              "rows": nrow, "channels": nchan, "visibilities": nvis,
+              "metric": "ms per device_dft_predict call, best of repeats around a synchronised call",
+              "value": cases[0]["fast_ms"], "unit": "ms", "repeat": args.repeat,
+              "torch_restatement": "fp64, rows in chunks of 16384: path, phase reduced by round(), torch.polar, "
+                                   "envelope exp, sum over components, weights, one rounding to complex64",
+              "cases": cases}
+    if args.config == "c3":  # the rows DESIGN.md 17 quotes
+        (ROOT / "profiles" / "dft_predict_c3.json").write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
+
 def restore(args):
     """ms per device_restore call (sparse and dense model) and per torch conv2d / fft2 restatement."""
     import torch
@@ -653,8 +758,8 @@ def restore(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "weights", "restore",
-                                      "gaincal"), required=True)
-    ap.add_argument("--config", default="c3", help="weights / restore / gaincal: the bench.py configuration whose inputs are used")
+                                      "gaincal", "dft"), required=True)
+    ap.add_argument("--config", default="c3", help="weights / restore / gaincal / dft: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--npix", type=int, default=2048)
@@ -696,6 +801,9 @@ def main():
         return
     if args.mode == "gaincal":
         print(json.dumps(gaincal(args)), flush=True)
+        return
+    if args.mode == "dft":
+        print(json.dumps(dft(args)), flush=True)
         return
     if args.mode == "mfs_clean":
         print(json.dumps(mfs_clean(args)), flush=True)
