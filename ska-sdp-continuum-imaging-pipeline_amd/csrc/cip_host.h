@@ -145,6 +145,11 @@ struct Workspace {
   void* restore_pinned = nullptr;
   hipEvent_t ev_restore = nullptr;
   std::vector<double> restore_key;
+  // the same for cip_ms_convolve's 1-D scale taps: the table on the device is
+  // (R, taps[0 .. 2R])
+  void* ms_pinned = nullptr;
+  hipEvent_t ev_ms = nullptr;
+  std::vector<double> ms_key;
 };
 
 // ---- cip_workspace.hip ----

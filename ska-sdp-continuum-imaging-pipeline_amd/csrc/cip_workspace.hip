@@ -82,6 +82,8 @@ static void destroy_workspace(Workspace* ws) {
   if (ws->pinned) (void)hipHostFree(ws->pinned);
   if (ws->restore_pinned) (void)hipHostFree(ws->restore_pinned);
   if (ws->ev_restore) (void)hipEventDestroy(ws->ev_restore);
+  if (ws->ms_pinned) (void)hipHostFree(ws->ms_pinned);
+  if (ws->ev_ms) (void)hipEventDestroy(ws->ev_ms);
   if (ws->side) {
     (void)hipStreamSynchronize(ws->side);
     (void)hipStreamDestroy(ws->side);

@@ -10,7 +10,8 @@ built on the two (`deconvolve.py`: Hogbom CLEAN, `cip_hogbom_clean`), the
 clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_restore`), uniform and Briggs imaging weights (`weighting.py`,
 `cip_imaging_weights`), multi-term multi-frequency synthesis (`mfs.py`,
-`cip_mfs_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`), the sky-model
+`cip_mfs_clean`), multiscale CLEAN (`multiscale.py`, `cip_ms_convolve`,
+`cip_ms_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`), the sky-model
 predict (`skymodel.py`, `cip_dft_predict`) and the `uvw_tiling` package.
 """
 
@@ -39,6 +40,19 @@ from .mfs import (  # noqa: E402
     mfs_clean,
     mfs_hessian,
     taylor_basis,
+)
+from . import multiscale  # noqa: E402
+from .multiscale import (  # noqa: E402
+    device_cross_psfs,
+    device_ms_clean,
+    device_ms_convolve,
+    device_ms_major_cycles,
+    device_ms_model,
+    device_scale_residuals,
+    ms_clean,
+    scale_radius,
+    scale_taps,
+    scale_weights,
 )
 from . import calibrate  # noqa: E402
 from .calibrate import (  # noqa: E402
@@ -106,6 +120,17 @@ __all__ = [
     "device_mfs_invert",
     "device_mfs_residual",
     "device_mfs_major_cycles",
+    "multiscale",
+    "scale_radius",
+    "scale_taps",
+    "scale_weights",
+    "ms_clean",
+    "device_ms_convolve",
+    "device_scale_residuals",
+    "device_cross_psfs",
+    "device_ms_clean",
+    "device_ms_model",
+    "device_ms_major_cycles",
     "calibrate",
     "solution_intervals",
     "GainCorrelator",

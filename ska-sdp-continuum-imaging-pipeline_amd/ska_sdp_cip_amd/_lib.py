@@ -1,6 +1,6 @@
 """
 ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h,
-include/cip_mfs.h, include/cip_cal.h and include/cip_dft.h).
+include/cip_mfs.h, include/cip_cal.h, include/cip_dft.h and include/cip_ms.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -313,6 +313,30 @@ DFT_PROTOTYPES = {
 }
 
 
+class MsResult(ctypes.Structure):
+    """Mirror of `cip_ms_result` (include/cip_ms.h)."""
+
+    _fields_ = [
+        ("niter_done", ctypes.c_int64),
+        ("stop_reason", ctypes.c_int32),
+        ("peak_scale", ctypes.c_int32),
+        ("peak", ctypes.c_double),
+        ("peak_index", ctypes.c_int64),
+    ]
+
+
+# And for include/cip_ms.h, the sixth (taps, select_weight and flux_scale are HOST arrays).
+MS_MAX_SCALES = 6  # CIP_MS_MAX_SCALES
+MS_MAX_RADIUS = 128  # CIP_MS_MAX_RADIUS
+MS_PROTOTYPES = {
+    "cip_ms_scale_radius": (_i32, [_f64, _f64]),
+    "cip_ms_scale_taps": (_i32, [_f64, _i64, _pf64]),
+    "cip_ms_convolve": (_i32, [_vp, _i64, _i64, _pf64, _i64, _vp, _vp]),
+    "cip_ms_clean": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _pf64, _pf64, _vp, _f64, _f64, _i64,
+                            _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MsResult)]),
+}
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
     global _LIB  # pylint: disable=global-statement
@@ -327,7 +351,7 @@ def lib() -> ctypes.CDLL:
         )
     so = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items(),
-                                      *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items()):
+                                      *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items(), *MS_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

@@ -35,19 +35,34 @@ _PF64 = ctypes.POINTER(ctypes.c_double)
 def _device_clean(residual, psf, hinv, stack, *, gain, threshold, niter, mask, model, psf_centre, inplace,
                   return_components, batch):
     """The minor cycle behind `device_hogbom_clean` (`stack` False: 2-D images,
-    no `hinv`, `cip_hogbom_clean`) and `mfs.device_mfs_clean` (`stack` True:
-    stacks and the host matrix `hinv`, `cip_mfs_clean`)."""
+    no `hinv`, `cip_hogbom_clean`), `mfs.device_mfs_clean` (`stack` True:
+    stacks and the host matrix `hinv`, `cip_mfs_clean`) and
+    `multiscale.device_ms_clean` (`stack` "ms": stacks, `hinv` is the pair of
+    host arrays (select_weight, flux_scale), `cip_ms_clean`)."""
     require_gpu()
     dev = residual.device
+    ms = stack == "ms"
+    stack = bool(stack)
     names, kind = (("residuals", "psfs"), "stack of 2-D images") if stack else (("residual", "psf"), "2-D image")
     for name, img in zip(names, (residual, psf)):
         if img.dim() != 2 + stack:
             raise ValueError(f"{name} must be a float64 {kind}, got {img.dtype} {tuple(img.shape)}")
         check_array(img, (torch.float64,), None, dev, name)
     shape = tuple(residual.shape[-2:])
-    # what cip_mfs_clean takes and cip_hogbom_clean does not: nterms (the stacks' first axis too) and hinv
+    # what cip_mfs_clean takes and cip_hogbom_clean does not: nterms (the stacks' first axis too) and hinv;
+    # cip_ms_clean: nscales and its two host arrays
     terms = matrix = ()
-    if stack:
+    if ms:
+        nscales = int(residual.shape[0])
+        host = [np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+                for x in hinv]
+        # nscales itself (1 .. 6) and the entries of the arrays are the library's to refuse
+        if any(x.shape != (nscales,) for x in host) or int(psf.shape[0]) != nscales * (nscales + 1) // 2:
+            raise ValueError(f"{nscales} residual scales need select_weight and flux_scale of shape ({nscales},) and "
+                             f"{nscales * (nscales + 1) // 2} cross PSFs, got {[x.shape for x in host]} and "
+                             f"{int(psf.shape[0])} PSFs")
+        terms, matrix = (nscales,), tuple(x.ctypes.data_as(_PF64) for x in host)
+    elif stack:
         nterms = int(residual.shape[0])
         h = np.ascontiguousarray(hinv.detach().cpu().numpy() if torch.is_tensor(hinv) else hinv, dtype=np.float64)
         if h.ndim != 2 or h.shape[0] != h.shape[1]:
@@ -70,13 +85,16 @@ def _device_clean(residual, psf, hinv, stack, *, gain, threshold, niter, mask, m
     if model is None:
         model = torch.zeros((*terms, *shape), dtype=torch.float64, device=dev)
     comp_index = comp_flux = None
+    comp_scale = (None,) if ms else ()  # cip_ms_clean's third component array: the scale of each component
     if return_components:
         comp_index = torch.empty(max(niter, 1), dtype=torch.int64, device=dev)
-        comp_flux = torch.empty((max(niter, 1), *terms), dtype=torch.float64, device=dev)
-    result = _lib.CleanResult()
-    call(dev, "cip_mfs_clean" if stack else "cip_hogbom_clean", res, *terms, shape[0], shape[1], psf,
-         int(psf.shape[-2]), int(psf.shape[-1]), cx, cy, *matrix, mask, float(gain), float(threshold), niter,
-         int(batch), STREAM, model, comp_index, comp_flux, ctypes.byref(result))
+        comp_flux = torch.empty((max(niter, 1), *(() if ms else terms)), dtype=torch.float64, device=dev)
+        if ms:
+            comp_scale = (torch.empty(max(niter, 1), dtype=torch.int64, device=dev),)
+    result = _lib.MsResult() if ms else _lib.CleanResult()
+    call(dev, "cip_ms_clean" if ms else "cip_mfs_clean" if stack else "cip_hogbom_clean", res, *terms, shape[0],
+         shape[1], psf, int(psf.shape[-2]), int(psf.shape[-1]), cx, cy, *matrix, mask, float(gain), float(threshold),
+         niter, int(batch), STREAM, model, comp_index, *comp_scale, comp_flux, ctypes.byref(result))
     info = {
         "niter_done": int(result.niter_done),
         "stop_reason": int(result.stop_reason),
@@ -84,15 +102,19 @@ def _device_clean(residual, psf, hinv, stack, *, gain, threshold, niter, mask, m
         "peak": float(result.peak),
         "peak_index": int(result.peak_index),
     }
+    if ms:
+        info["peak_scale"] = int(result.peak_scale)
     if return_components:
         info["comp_index"] = comp_index[: info["niter_done"]]
         info["comp_flux"] = comp_flux[: info["niter_done"]]
+        if ms:
+            info["comp_scale"] = comp_scale[0][: info["niter_done"]]
     return model, res, info
 
 
 def _host_clean(device_clean, residual, psf, *hinv, mask, model, return_components, device, **kw):
-    """`hogbom_clean` and `mfs.mfs_clean`: `device_clean` on copies of host or
-    device arrays, numpy in -> numpy out."""
+    """`hogbom_clean`, `mfs.mfs_clean` and `multiscale.ms_clean`: `device_clean`
+    on copies of host or device arrays, numpy in -> numpy out."""
     require_gpu()
     dev = target_device(device)
     numpy_in = isinstance(residual, np.ndarray)
@@ -109,8 +131,9 @@ def _host_clean(device_clean, residual, psf, *hinv, mask, model, return_componen
         if numpy_in:
             model_d, res_d = model_d.cpu().numpy(), res_d.cpu().numpy()
             if return_components:
-                info["comp_index"] = info["comp_index"].cpu().numpy()
-                info["comp_flux"] = info["comp_flux"].cpu().numpy()
+                for key in ("comp_index", "comp_flux", "comp_scale"):
+                    if key in info:
+                        info[key] = info[key].cpu().numpy()
     return model_d, res_d, info
 
 

@@ -30,6 +30,14 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     device_hogbom_clean on term 0 at the same shapes and a
                     torch loop that restates the operator, all in the same
                     run; also written to profiles/mfs_clean_c3.json
+  --mode ms_clean   device_ms_clean (the multiscale minor cycle, scales --widths)
+                    on the scene of --mode clean smoothed with every scale,
+                    once with a --patch^2 cut of the PSF and once with the full
+                    PSF: microseconds per iteration and the GB/s that implies
+                    at 24 S B per window pixel, beside device_hogbom_clean at
+                    the same shapes in the same run; and device_ms_convolve on
+                    the full image at radius 32 and 128: ms and GB/s at 32 B
+                    per pixel; also written to profiles/ms_clean_c3.json
   --mode weights    uniform imaging weights (weighting.py) on bench.py's C3
                     inputs and geometry: density / statistics / apply and the
                     one-shot call, best of --repeat; the synchronous
@@ -331,6 +339,105 @@ def mfs_clean(args):
     result["value"] = result["full_psf"]["us_per_iteration"]
     if npix == 8192 and nterms == 2:  # the row DESIGN.md 15 quotes
         (ROOT / "profiles" / "mfs_clean_c3.json").write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
+
+def ms_clean(args):
+    """us per iteration of device_ms_clean and of device_hogbom_clean at the same shapes; GB/s of device_ms_convolve."""
+    import torch
+
+    from ska_sdp_cip_amd import _lib, deconvolve, gridder, multiscale, synthetic as syn
+
+    dev = torch.device("cuda", 0)
+    npix, gain, widths = args.npix, args.gain, [float(w) for w in args.widths]
+    nscales = len(widths)
+    uvw_h = syn.uvw_tracks(args.rows, 64, array_radius_m=4000.0)
+    freq_h = syn.channel_frequencies(args.nchan)
+    px = syn.pixel_size_for_grid(uvw_h, freq_h, npix, support=8)
+    uvw, freq = torch.from_numpy(uvw_h).to(dev), torch.from_numpy(freq_h).to(dev)
+    psf_full, _ = gridder.device_ms2dirty(uvw, freq, None, None, npix, npix, px, px, support=8, psf=True,
+                                          normalise=True)
+    _lib.lib().cip_release_workspace()  # the invert's grid is not needed any more
+    rng = np.random.default_rng(20241019)
+    where = (rng.integers(0, npix, args.sources), rng.integers(0, npix, args.sources))
+    fluxes = rng.lognormal(0.0, 1.0, args.sources)
+
+    def sync_time(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def case(pn, niter):
+        o = npix // 2 - pn // 2  # the cut keeps the peak at (pn // 2, pn // 2)
+        psf = psf_full if pn == npix else psf_full[o:o + pn, o:o + pn].contiguous()
+        c = pn // 2
+
+        def window(i, j):
+            return max(0, i - c), min(npix, i - c + pn), max(0, j - c), min(npix, j - c + pn)
+
+        image = torch.zeros((npix, npix), dtype=torch.float64, device=dev)
+        for i, j, flux in zip(*where, fluxes):
+            a0, a1, b0, b1 = window(int(i), int(j))
+            image[a0:a1, b0:b1] += float(flux) * psf[a0 - i + c:a1 - i + c, b0 - j + c:b1 - j + c]
+        cross = multiscale.device_cross_psfs(psf, widths)
+        select_weight, flux_scale = multiscale.scale_weights(cross, widths)
+        scaled = multiscale.device_scale_residuals(image, widths)
+
+        def ms_run(n):
+            res = scaled.clone()
+            dt, (_, _, info) = sync_time(lambda: multiscale.device_ms_clean(
+                res, cross, select_weight, flux_scale, gain=gain, niter=n, inplace=True, return_components=True,
+                batch=args.batch))
+            return dt, info
+
+        def hogbom_run(n):
+            res = image.clone()
+            dt, (_, _, info) = sync_time(lambda: deconvolve.device_hogbom_clean(res, psf, gain=gain, niter=n,
+                                                                                inplace=True, batch=args.batch))
+            return dt, info
+
+        ms_run(min(niter, 8))  # warm-up: workspace, kernels
+        dt, info = min((ms_run(niter) for _ in range(args.repeat)), key=lambda r: r[0])
+        n = info["niter_done"]
+        pixels = 0
+        for flat in info["comp_index"].cpu().tolist():
+            a0, a1, b0, b1 = window(*divmod(flat, npix))
+            pixels += (a1 - a0) * (b1 - b0)
+        hogbom_run(min(niter, 8))
+        dt_h, info_h = min((hogbom_run(niter) for _ in range(args.repeat)), key=lambda r: r[0])
+        us, us_h = dt / n * 1e6, dt_h / info_h["niter_done"] * 1e6
+        return {"psf_npix": pn, "niter": n, "stop": info["stop"], "us_per_iteration": round(us, 2),
+                "components_per_scale": torch.bincount(info["comp_scale"], minlength=nscales).cpu().tolist(),
+                "window_pixels_mean": round(pixels / n), "bytes_per_window_pixel": 24 * nscales,
+                "GBs_at_model_bytes": round(24.0 * nscales * pixels / dt / 1e9, 1),
+                "hogbom_us_per_iteration": round(us_h, 2), "hogbom_niter": info_h["niter_done"],
+                "ratio_to_hogbom": round(us / us_h, 2), "byte_model_ratio": float(nscales),
+                "select_weight": select_weight.tolist(), "flux_scale": flux_scale.tolist()}
+
+    def convolve(radius, width):
+        taps = multiscale.scale_taps(width, radius)
+        out = torch.empty_like(psf_full)
+        run = lambda: multiscale.device_ms_convolve(psf_full, None, taps=taps, out=out)  # noqa: E731
+        run()
+        dt = min(sync_time(run)[0] for _ in range(max(args.repeat, 3)))
+        # the input read, the workspace image written and read, the output written
+        return {"radius": radius, "width": width, "ms": round(dt * 1e3, 3),
+                "GBs_at_32B_per_pixel": round(32.0 * npix * npix / dt / 1e9, 1),
+                "Gtaps_per_s": round(2.0 * (2 * radius + 1) * npix * npix / dt / 1e9, 1)}
+
+    result = {"data": "synthetic (lognormal point sources convolved with a PSF from device_ms2dirty(psf=True) on real "
+                      "uvw tracks, then smoothed with every scale)",
+              "npix": npix, "widths": widths, "sources": args.sources, "gain": gain, "rows": args.rows,
+              "channels": args.nchan, "batch": args.batch or _lib.CIP_CLEAN_DEFAULT_BATCH, "repeat": args.repeat,
+              "metric": "us per iteration (device_ms_clean, full PSF, fp64)", "unit": "us/iteration"}
+    result["convolve"] = [convolve(32, 12.0), convolve(128, 49.0)]
+    result["patch"] = case(min(args.patch, npix), args.niter)
+    result["full_psf"] = case(npix, min(args.niter, args.full_niter))
+    result["value"] = result["full_psf"]["us_per_iteration"]
+    if npix == 8192 and nscales == 4:  # the row DESIGN.md 18 quotes
+        (ROOT / "profiles" / "ms_clean_c3.json").write_text(json.dumps(result, indent=1) + "\n")
     return result
 
 
@@ -757,8 +864,8 @@ def restore(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "weights", "restore",
-                                      "gaincal", "dft"), required=True)
+    ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "ms_clean", "weights",
+                                      "restore", "gaincal", "dft"), required=True)
     ap.add_argument("--config", default="c3", help="weights / restore / gaincal / dft: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
@@ -782,7 +889,10 @@ def main():
     ap.add_argument("--restore-npix", type=int, default=8192, help="restore: image edge")
     ap.add_argument("--components", type=int, default=10_000, help="restore: non-zero pixels of the sparse model")
     ap.add_argument("--patch", type=int, default=512,
-                    help="restore: edge of the dense model patch; mfs_clean: edge of the PSF patch")
+                    help="restore: edge of the dense model patch; mfs_clean / ms_clean: edge of the PSF patch")
+    ap.add_argument("--widths", type=float, nargs="+", default=[0.0, 4.0, 8.0, 16.0],
+                    help="ms_clean: scale FWHMs in pixels")
+    ap.add_argument("--full-niter", type=int, default=200, help="ms_clean: iterations of the full-PSF case at most")
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
 
@@ -807,6 +917,9 @@ def main():
         return
     if args.mode == "mfs_clean":
         print(json.dumps(mfs_clean(args)), flush=True)
+        return
+    if args.mode == "ms_clean":
+        print(json.dumps(ms_clean(args)), flush=True)
         return
     if args.mode == "clean":
         if args.psf_npix is None:
