@@ -12,28 +12,49 @@ namespace cip {
 // (sets the fixed-point scale): per-block partials come from the planner's
 // place pass (cip_plan.hip); this reduces them in a fixed order.
 
-// 1024 threads, 4 independent partial sums per thread (the loads of one
-// thread are not serialised behind one accumulator); fixed order throughout.
-__global__ __launch_bounds__(1024) void prep_final_kernel(const double* partial, int nblocks, double* out2) {
-  double sum[4] = {0.0, 0.0, 0.0, 0.0}, mx = 0.0;
-  for (int i0 = threadIdx.x; i0 < nblocks; i0 += 4 * 1024) {
-    if (i0 + 3 * 1024 < nblocks) {
-      // all 4 in range: the loads issue back to back (same order of sums)
-      double2 p[4];
+// The order of the sum is part of the result. It is that of a block of 1024
+// threads: thread t sums the partials t + 1024 k + 4096 j into 4 accumulators
+// (k = 0..3, each over j ascending), combines them as (0 + 1) + (2 + 3), a
+// 64-lane xor-shuffle tree (d = 32 .. 1) gives each of the 16 waves its total,
+// and the wave totals are added in wave order. Two launches of one-wave blocks
+// compute it with no LDS - the 16 waves' totals by a block each, then their
+// sum by one lane - so each block is resident beside the scatter of the call
+// before, where the 16-wave block waited for a scatter block to
+// retire.
+constexpr int kPrepWaves = 16, kPrepAcc = 4;
+constexpr int kPrepThreads = 64 * kPrepWaves;  // of the order's block
+constexpr int kPrepStride = kPrepAcc * kPrepThreads;
+constexpr int kPrepUnroll = 4;  // strides whose loads issue together
+static_assert(2 * kPrepWaves <= kPrepFinalScratch, "a {sum, max} pair per wave behind the partials");
+
+// block w: the total of the order's wave w -> totals[2 w], its maximum -> totals[2 w + 1]
+__global__ __launch_bounds__(64) void prep_wave_totals_kernel(const double* partial, int nblocks, double* totals) {
+  const double2* p2 = reinterpret_cast<const double2*>(partial);
+  double sum[kPrepAcc] = {0.0, 0.0, 0.0, 0.0}, mx = 0.0;
+  int i0 = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  // kPrepUnroll strides with every index in range: the loads issue back to
+  // back (the same order of sums: j ascending per accumulator)
+  for (; (int64_t)i0 + (kPrepUnroll - 1) * kPrepStride + (kPrepAcc - 1) * kPrepThreads < nblocks;
+       i0 += kPrepUnroll * kPrepStride) {
+    double2 p[kPrepUnroll][kPrepAcc];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) p[k] = reinterpret_cast<const double2*>(partial)[i0 + k * 1024];
+    for (int j = 0; j < kPrepUnroll; ++j)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sum[k] += p[k].x;
-        mx = fmax(mx, p[k].y);
+      for (int k = 0; k < kPrepAcc; ++k) p[j][k] = p2[i0 + j * kPrepStride + k * kPrepThreads];
+#pragma unroll
+    for (int j = 0; j < kPrepUnroll; ++j)
+#pragma unroll
+      for (int k = 0; k < kPrepAcc; ++k) {
+        sum[k] += p[j][k].x;
+        mx = fmax(mx, p[j][k].y);
       }
-      continue;
-    }
+  }
+  for (; i0 < nblocks; i0 += kPrepStride) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int i = i0 + k * 1024;
+    for (int k = 0; k < kPrepAcc; ++k) {
+      const int64_t i = (int64_t)i0 + k * kPrepThreads;
       if (i < nblocks) {
-        const double2 p = reinterpret_cast<const double2*>(partial)[i];
+        const double2 p = p2[i];
         sum[k] += p.x;
         mx = fmax(mx, p.y);
       }
@@ -44,25 +65,27 @@ __global__ __launch_bounds__(1024) void prep_final_kernel(const double* partial,
     s += __shfl_xor(s, d, 64);
     mx = fmax(mx, __shfl_xor(mx, d, 64));
   }
-  __shared__ double ss[16], sm[16];
-  if ((threadIdx.x & 63) == 0) {
-    ss[threadIdx.x >> 6] = s;
-    sm[threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
   if (threadIdx.x == 0) {
-    double t = 0.0, m = 0.0;
-    for (int w = 0; w < 16; ++w) {
-      t += ss[w];
-      m = fmax(m, sm[w]);
-    }
-    out2[0] = t;
-    out2[1] = m;
+    totals[2 * blockIdx.x] = s;
+    totals[2 * blockIdx.x + 1] = mx;
   }
 }
 
-hipError_t launch_prep_final(const double* partial, int nblocks, double* out2, hipStream_t s) {
-  prep_final_kernel<<<dim3(1), dim3(1024), 0, s>>>(partial, nblocks, out2);
+__global__ __launch_bounds__(64) void prep_final_kernel(const double* totals, double* out2) {
+  if (threadIdx.x != 0) return;
+  double t = 0.0, m = 0.0;
+  for (int w = 0; w < kPrepWaves; ++w) {
+    t += totals[2 * w];
+    m = fmax(m, totals[2 * w + 1]);
+  }
+  out2[0] = t;
+  out2[1] = m;
+}
+
+hipError_t launch_prep_final(double* partial, int nblocks, double* out2, hipStream_t s) {
+  double* totals = partial + 2 * (int64_t)nblocks;
+  prep_wave_totals_kernel<<<dim3(kPrepWaves), dim3(64), 0, s>>>(partial, nblocks, totals);
+  prep_final_kernel<<<dim3(1), dim3(64), 0, s>>>(totals, out2);
   return hipGetLastError();
 }
 

@@ -107,9 +107,11 @@ hipError_t launch_gather_i64(const int64_t* src, int64_t stride, int64_t count, 
                              hipStream_t s);
 
 // ---- gridding (cip_grid.hip) -----------------------------------------------
-// out2 = {sum, max} of the place pass's 2 * nblocks partials
+// out2 = {sum, max} of the place pass's 2 * nblocks partials; `partial` holds
+// kPrepFinalScratch more doubles behind them (the reduction's wave totals)
+constexpr int kPrepFinalScratch = 32;
 hipError_t launch_add_scalar(const double* src, double* dst, hipStream_t s);
-hipError_t launch_prep_final(const double* partial, int nblocks, double* out2, hipStream_t s);
+hipError_t launch_prep_final(double* partial, int nblocks, double* out2, hipStream_t s);
 // The plan as the scatter and the degridder read it: the visibilities and the
 // planner's buffers that index them (the degridder reads neither vis, wgt,
 // tile_run_off nor perm).

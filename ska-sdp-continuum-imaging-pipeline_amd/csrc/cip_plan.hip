@@ -10,9 +10,49 @@
 namespace cip {
 
 // ---------------------------------------------------------------- scan ----
-constexpr int kScanThreads = 1024;
+// One wave per block and no LDS: the planner's scans run on low-priority
+// streams beside the 64 x 64 scatter, whose two blocks per CU leave 96 VGPRs
+// per SIMD and no LDS - a block of 16 waves with an LDS exchange
+// waits there for a scatter block to retire. The wave takes its 4096 items in
+// 16 rounds of 256 (4 consecutive items per lane: the wave's loads cover 2 KB
+// of consecutive addresses), scans the 64 lane sums of a round with DPP moves
+// and carries the rounds' total in scalar registers.
+constexpr int kScanThreads = 64;
 constexpr int kScanItems = 4;
-constexpr int64_t kScanBlock = (int64_t)kScanThreads * kScanItems;
+constexpr int kScanRound = kScanThreads * kScanItems;  // items per round
+constexpr int kScanRounds = 16;
+constexpr int kScanBatch = 4;  // rounds whose loads issue together
+constexpr int64_t kScanBlock = (int64_t)kScanRound * kScanRounds;
+static_assert(kScanBlock == 4096, "scan_tmp_elems and every caller's scratch size assume 4096 items per block");
+static_assert(kScanRounds % kScanBatch == 0, "whole batches");
+
+// v of the lane CTRL names (a DPP move); lanes without a source, and the rows
+// outside ROW_MASK, get 0
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int64_t dpp_or_zero(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xf, false);
+  const uint32_t hi =
+      (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)((uint64_t)v >> 32), CTRL, ROW_MASK, 0xf, false);
+  return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
+}
+// inclusive scan over the 64 lanes (all active): Hillis-Steele inside each row
+// of 16 lanes (row_shr 1, 2, 4, 8), then row 0's total into row 1 and row 2's
+// into row 3 (row_bcast:15), then lane 31's total into rows 2 and 3
+// (row_bcast:31). VALU only: __shfl_up is an LDS-crossbar ds_bpermute per step.
+__device__ __forceinline__ int64_t wave_scan_incl(int64_t x) {
+  x += dpp_or_zero<0x111, 0xf>(x);
+  x += dpp_or_zero<0x112, 0xf>(x);
+  x += dpp_or_zero<0x114, 0xf>(x);
+  x += dpp_or_zero<0x118, 0xf>(x);
+  x += dpp_or_zero<0x142, 0xa>(x);
+  x += dpp_or_zero<0x143, 0xc>(x);
+  return x;
+}
+__device__ __forceinline__ int64_t read_lane63(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), 63);
+  return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
+}
 
 // RUNS: the input is the runs (n - 1 of them): item k is run k's length, item
 // n - 1 is 0, and the scan goes to `data` (the fused run-length pass of the
@@ -27,80 +67,82 @@ __device__ __forceinline__ int64_t run_length_at(const void* __restrict__ src, i
     return (int64_t)(rec & 0xffff) - (int64_t)((rec >> 16) & 0xffff);
   }
 }
+// The block's rounds. FULL: every item of the block has a value of its own
+// (all of them in range: the loads of a batch issue back to back; a per-item
+// branch waits for each in turn); otherwise items from `nin` on count 0 and
+// only items below n are stored.
+template <int RUNS, bool FULL>
+__device__ __forceinline__ int64_t scan_rounds(int64_t* data, int64_t n, int64_t nin, const void* __restrict__ runs,
+                                               int64_t b0, int lane) {
+  int64_t carry = 0;  // the total of the rounds before (wave-uniform)
+#pragma unroll
+  for (int r0 = 0; r0 < kScanRounds; r0 += kScanBatch) {
+    if (!FULL && b0 + (int64_t)r0 * kScanRound >= n) break;  // (uniform)
+    int64_t v[kScanBatch][kScanItems];
+#pragma unroll
+    for (int q = 0; q < kScanBatch; ++q) {
+      const int64_t base = b0 + (int64_t)(r0 + q) * kScanRound + (int64_t)lane * kScanItems;
+#pragma unroll
+      for (int i = 0; i < kScanItems; ++i) {
+        if constexpr (FULL) {
+          if constexpr (RUNS) v[q][i] = run_length_at<RUNS>(runs, base + i);
+          else v[q][i] = data[base + i];
+        } else {
+          v[q][i] = 0;
+          if (base + i < nin) {
+            if constexpr (RUNS) v[q][i] = run_length_at<RUNS>(runs, base + i);
+            else v[q][i] = data[base + i];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kScanBatch; ++q) {
+      const int64_t base = b0 + (int64_t)(r0 + q) * kScanRound + (int64_t)lane * kScanItems;
+      int64_t tsum = 0;
+#pragma unroll
+      for (int i = 0; i < kScanItems; ++i) tsum += v[q][i];
+      const int64_t incl = wave_scan_incl(tsum);
+      int64_t run = carry + (incl - tsum);
+#pragma unroll
+      for (int i = 0; i < kScanItems; ++i) {
+        if (FULL || base + i < n) data[base + i] = run;
+        run += v[q][i];
+      }
+      carry += read_lane63(incl);
+    }
+  }
+  return carry;
+}
 template <int RUNS>
 __global__ __launch_bounds__(kScanThreads) void scan_local_kernel(int64_t* data, int64_t n, int64_t* block_sums,
                                                                   const void* __restrict__ runs) {
-  __shared__ int64_t wave_tot[kScanThreads / 64];
-  const int64_t base = (int64_t)blockIdx.x * kScanBlock + (int64_t)threadIdx.x * kScanItems;
-  int64_t v[kScanItems];
-  int64_t tsum = 0;
-  // threads with all their items in range load them unconditionally (the
-  // loads issue back to back; a per-item branch waits for each in turn)
-  if (base + kScanItems <= (RUNS ? n - 1 : n)) {
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-      if constexpr (RUNS) {
-        v[i] = run_length_at<RUNS>(runs, base + i);
-      } else {
-        v[i] = data[base + i];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-      if constexpr (RUNS) {
-        v[i] = 0;
-        if (base + i < n - 1) v[i] = run_length_at<RUNS>(runs, base + i);
-      } else {
-        v[i] = (base + i < n) ? data[base + i] : 0;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i) tsum += v[i];
-  // inclusive wave scan of the thread sums
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t incl = tsum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int64_t o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    int64_t t = (lane < kScanThreads / 64) ? wave_tot[lane] : 0;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      int64_t o = __shfl_up(t, d, 64);
-      if (lane >= d) t += o;
-    }
-    if (lane < kScanThreads / 64) wave_tot[lane] = t;  // inclusive over waves
-  }
-  __syncthreads();
-  int64_t run = incl - tsum + (wave > 0 ? wave_tot[wave - 1] : 0);
-#pragma unroll
-  for (int i = 0; i < kScanItems; ++i) {
-    if (base + i < n) data[base + i] = run;
-    run += v[i];
-  }
-  if (threadIdx.x == kScanThreads - 1) block_sums[blockIdx.x] = run;
+  const int lane = threadIdx.x;
+  const int64_t b0 = (int64_t)blockIdx.x * kScanBlock;
+  const int64_t nin = RUNS ? n - 1 : n;  // items with a value of their own
+  const int64_t total = b0 + kScanBlock <= nin ? scan_rounds<RUNS, true>(data, n, nin, runs, b0, lane)
+                                               : scan_rounds<RUNS, false>(data, n, nin, runs, b0, lane);
+  if (lane == 0) block_sums[blockIdx.x] = total;
 }
 
-__global__ void scan_add_kernel(int64_t* data, int64_t n, const int64_t* offsets) {
+// data[i] += offsets[block of i]: one wave per SIMD (256 threads, 16 items
+// each), so it also fits beside the scatter
+constexpr int kScanAddThreads = 256;
+constexpr int kScanAddItems = (int)(kScanBlock / kScanAddThreads);
+__global__ __launch_bounds__(kScanAddThreads) void scan_add_kernel(int64_t* data, int64_t n, const int64_t* offsets) {
   const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
   const int64_t off = offsets[blockIdx.x];
-  if (i + (int64_t)(kScanItems - 1) * kScanThreads < n) {
-    int64_t v[kScanItems];
+  if ((int64_t)(blockIdx.x + 1) * kScanBlock <= n) {
+    int64_t v[kScanAddItems];
 #pragma unroll
-    for (int k = 0; k < kScanItems; ++k) v[k] = data[i + (int64_t)k * kScanThreads];
+    for (int k = 0; k < kScanAddItems; ++k) v[k] = data[i + (int64_t)k * kScanAddThreads];
 #pragma unroll
-    for (int k = 0; k < kScanItems; ++k) data[i + (int64_t)k * kScanThreads] = v[k] + off;
+    for (int k = 0; k < kScanAddItems; ++k) data[i + (int64_t)k * kScanAddThreads] = v[k] + off;
     return;
   }
 #pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t j = i + (int64_t)k * kScanThreads;
+  for (int k = 0; k < kScanAddItems; ++k) {
+    const int64_t j = i + (int64_t)k * kScanAddThreads;
     if (j < n) data[j] += off;
   }
 }
@@ -131,7 +173,7 @@ static hipError_t scan_impl(int64_t* data, int64_t n, int64_t* tmp, ScanLengths 
   if (e != hipSuccess || nb == 1) return e;
   e = scan_impl(tmp, nb, tmp + nb, ScanLengths{0, nullptr}, s);
   if (e != hipSuccess) return e;
-  scan_add_kernel<<<dim3((unsigned)nb), dim3(kScanThreads), 0, s>>>(data, n, tmp);
+  scan_add_kernel<<<dim3((unsigned)nb), dim3(kScanAddThreads), 0, s>>>(data, n, tmp);
   return hipGetLastError();
 }
 
@@ -735,32 +777,71 @@ __device__ __forceinline__ int64_t radix_count(int64_t b, int64_t n, const int64
   return rem < kRadixBlock ? rem : kRadixBlock;
 }
 
-__global__ __launch_bounds__(kRadixThreads) void radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n,
-                                                                   const int64_t* __restrict__ blk_cnt, int64_t nsub,
-                                                                   int G, int shift, int64_t ngroups,
-                                                                   int64_t* __restrict__ hist) {
-  __shared__ unsigned cnt[256];
-  cnt[threadIdx.x] = 0u;
-  __syncthreads();
+// The group's digit histogram in one wave's registers, no LDS (the kernel runs
+// beside the 64 x 64 scatter, which leaves none: DESIGN 10). Lane l counts the
+// digits l, l + 64, l + 128 and l + 192. Per step of 64 keys, 8 ballots give
+// the lanes' digit bits as wave-uniform masks m[0..7]; the keys whose low 6
+// digit bits equal l are AND_b (m[b] ^ flip[b]) with flip[b] = bit b of l ? 0 :
+// ~0 (per-lane constants), and the four (bit 6, bit 7) combinations - scalar
+// ANDs, the valid lanes folded in - split them over the lane's four digits:
+// each count advances by a popcount.
+constexpr int kRadixHistThreads = 64;
+constexpr int kRadixHistBatch = 16;  // steps whose key loads issue together
+static_assert(kRadixBlock % (64 * kRadixHistBatch) == 0, "whole batches in a full sub-block");
+
+__device__ __forceinline__ void radix_hist_step(uint32_t digit, bool valid, const uint32_t (&flip)[6],
+                                                unsigned (&cnt)[4]) {
+  unsigned long long m[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) m[b] = __ballot((digit >> b) & 1u);
+  const unsigned long long vm = __ballot(valid);
+  uint32_t lo = 0xffffffffu, hi = 0xffffffffu;
+#pragma unroll
+  for (int b = 0; b < 6; ++b) {
+    lo &= (uint32_t)m[b] ^ flip[b];
+    hi &= (uint32_t)(m[b] >> 32) ^ flip[b];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned long long sel = vm & ((q & 1) ? m[6] : ~m[6]) & ((q & 2) ? m[7] : ~m[7]);
+    cnt[q] += (unsigned)__popc(lo & (uint32_t)sel) + (unsigned)__popc(hi & (uint32_t)(sel >> 32));
+  }
+}
+
+__global__ __launch_bounds__(kRadixHistThreads) void radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n,
+                                                                       const int64_t* __restrict__ blk_cnt,
+                                                                       int64_t nsub, int G, int shift,
+                                                                       int64_t ngroups, int64_t* __restrict__ hist) {
+  const int lane = threadIdx.x;
+  uint32_t flip[6];
+#pragma unroll
+  for (int b = 0; b < 6; ++b) flip[b] = ((lane >> b) & 1) ? 0u : 0xffffffffu;
+  unsigned cnt[4] = {0u, 0u, 0u, 0u};
   const int64_t b0 = (int64_t)blockIdx.x * G;
   const int64_t b1 = b0 + G < nsub ? b0 + G : nsub;
   for (int64_t b = b0; b < b1; ++b) {
-    const int64_t cnt_b = radix_count(b, n, blk_cnt);
+    const int cnt_b = (int)radix_count(b, n, blk_cnt);  // <= kRadixBlock
     const uint32_t* kb = keys + b * kRadixBlock;
-    if (cnt_b == kRadixBlock) {
-      // full sub-block: the loads issue back to back (the loop below waits for each)
-      uint32_t kk[kRadixPer];
+    for (int i0 = 0; i0 < cnt_b; i0 += 64 * kRadixHistBatch) {
+      uint32_t kk[kRadixHistBatch];
+      if (i0 + 64 * kRadixHistBatch <= cnt_b) {
+        // a whole batch: the loads issue back to back (a guarded load waits for each)
 #pragma unroll
-      for (int k = 0; k < kRadixPer; ++k) kk[k] = kb[threadIdx.x + k * kRadixThreads];
+        for (int k = 0; k < kRadixHistBatch; ++k) kk[k] = kb[i0 + 64 * k + lane];
 #pragma unroll
-      for (int k = 0; k < kRadixPer; ++k) atomicAdd(&cnt[(kk[k] >> shift) & 255u], 1u);
-    } else {
-      for (int64_t i = threadIdx.x; i < cnt_b; i += kRadixThreads) atomicAdd(&cnt[(kb[i] >> shift) & 255u], 1u);
+        for (int k = 0; k < kRadixHistBatch; ++k) radix_hist_step((kk[k] >> shift) & 255u, true, flip, cnt);
+      } else {
+        for (int i = i0; i < cnt_b; i += 64) {  // (uniform)
+          const bool valid = i + lane < cnt_b;
+          const uint32_t key = valid ? kb[i + lane] : 0u;
+          radix_hist_step((key >> shift) & 255u, valid, flip, cnt);
+        }
+      }
     }
   }
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * ngroups + blockIdx.x] = cnt[threadIdx.x];
-  if (blockIdx.x == 0 && threadIdx.x == 0) hist[256 * ngroups] = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) hist[(int64_t)(lane + 64 * q) * ngroups + blockIdx.x] = cnt[q];
+  if (blockIdx.x == 0 && lane == 0) hist[256 * ngroups] = 0;
 }
 
 // hg[d * ngroups + g] = sum of hist0[d * nsub + b] over the G sub-blocks of
@@ -873,8 +954,8 @@ hipError_t launch_radix_hist(const uint32_t* keys, int64_t n, const int64_t* blk
                              int64_t* hist, hipStream_t s) {
   if (nsub == 0) return hipSuccess;
   const int64_t ngroups = (nsub + G - 1) / G;
-  radix_hist_kernel<<<dim3((unsigned)ngroups), dim3(kRadixThreads), 0, s>>>(keys, n, blk_cnt, nsub, G, shift,
-                                                                          ngroups, hist);
+  radix_hist_kernel<<<dim3((unsigned)ngroups), dim3(kRadixHistThreads), 0, s>>>(keys, n, blk_cnt, nsub, G, shift,
+                                                                              ngroups, hist);
   return hipGetLastError();
 }
 

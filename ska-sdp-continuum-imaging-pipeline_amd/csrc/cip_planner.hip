@@ -67,7 +67,7 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
   CIP_ALLOC(blk_cnt, int64_t, "blk_cnt", nblk)
   CIP_ALLOC(park_key, uint32_t, "park_key", (int64_t)nblk * 4096)
   CIP_ALLOC(park_run, uint64_t, "park_run", (int64_t)nblk * 4096)
-  CIP_ALLOC(partial, double, "prep_partial", 2 * nblk)
+  CIP_ALLOC(partial, double, "prep_partial", 2 * nblk + kPrepFinalScratch)
   // the place pass also writes radix pass 0's histogram per place block; summed
   // per radix group of g0 blocks, its scan's last entry = runs
   const int g0 = radix_group(0), g1 = radix_group(1);
@@ -374,7 +374,7 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
     // the plan's buffers are read-only here; only the weight reduction runs
     // (it places nothing, so it never sets error bit 0)
     const int nblk = plan_place_blocks(m.nvis);
-    CIP_ALLOC(partial, double, "prep_partial_reuse", 2 * nblk)
+    CIP_ALLOC(partial, double, "prep_partial_reuse", 2 * nblk + kPrepFinalScratch)
     CIP_HIP_CHECK(launch_prep_reduce(m, rq.vis, vis_dtype, rq.wgt, wgt_dtype, out->g, err, partial, s));
     CIP_HIP_CHECK(launch_prep_final(partial, nblk, red, s));
     unsigned* h = (unsigned*)pinned(ws, 4 * sizeof(double));

@@ -5,7 +5,7 @@ import csv
 import sys
 
 path = sys.argv[1]
-pat = sys.argv[2] if len(sys.argv) > 2 else "scatter_kernel"
+pat = sys.argv[2] if len(sys.argv) > 2 else "cip::scatter_kernel<"  # ("scatter_kernel" alone also names radix_scatter_kernel)
 min_us = float(sys.argv[3]) if len(sys.argv) > 3 else 15.0
 nsteps = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 rows = list(csv.DictReader(open(path)))
