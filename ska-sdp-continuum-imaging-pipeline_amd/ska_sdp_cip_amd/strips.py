@@ -20,16 +20,22 @@ is all-reduced and divided out in pass B's epilogue. Traffic per rank at C4
 (16384^2 grid, 8 ranks): halo 1.8 MB, all-to-all 224 MB, image rows 64 MB -
 against a 4 GiB partial-grid reduce for row (weak) sharding.
 
-The per-rank stages are backend-independent (`HipStripBackend` runs them
-through libcip_hip.so; tests plug in a CPU restatement); `invert_strips` wires
-them with torch.distributed collectives (RCCL, or gloo on CPU tensors), and
-`invert_strips_local` runs all ranks' stages in one process (one device),
-exchanging in memory - the single-GPU check of the decomposition.
+The per-rank stages are a `StripBackend` (`HipStripBackend` runs them through
+libcip_hip.so; tests plug in a CPU restatement). Their order is written once,
+in `_invert`: a driver over the ranks present in the process and the planes
+of their buffers (2-D is the one-plane case), which moves data between ranks
+only through an exchange object - halo ring, weight-sum reduction, live-mask
+all-gather, all-to-all, image-row gather. `invert_strips` runs it for one rank
+with torch.distributed collectives (`_DistExchange`: RCCL, or gloo on CPU
+tensors); `invert_strips_local` for all ranks in one process on one device
+with the exchanges in memory (`_LocalExchange`) - the single-GPU check of the
+decomposition, running the distributed path's own stages.
 """
 
 from __future__ import annotations
 
 import os
+import time
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -330,7 +336,88 @@ def strip_buffer_rows(layout: StripLayout, r: int) -> tuple[int, int]:
     return y0, y1 - y0 + layout.halo
 
 
-class HipStripBackend:
+class StripBackend:
+    """One rank's stages of the strip invert: everything the driver (`_invert`)
+    asks of a backend. The stages below must be implemented; the attributes and
+    the two optional stages after them have defaults. A backend also carries
+    `npix_y` (the image rows' length)."""
+
+    nplanes = 1     # w planes in the buffer (1: the 2-D gridder)
+    single = False  # the packed class: pass-A blocks cross the all-to-all as complex64
+    device = None   # the torch device of the buffers (None: the host)
+    ranks = None    # invert_strips_local's per-rank backends, kept between calls
+
+    def spawn(self) -> "StripBackend":
+        """A backend of the same configuration (another rank's, for the single-process emulation)."""
+        raise NotImplementedError
+
+    def bind(self, layout: StripLayout, rank: int) -> "StripBackend":
+        """Hold rank `rank`'s strip + halo rows of `layout` (`strip_buffer_rows`)."""
+        raise NotImplementedError
+
+    def grid_strip(self, data: "StripData", freq):
+        """Grid the strip -> (buffer (nrows, nu, 2) f64, (nplanes, nrows, nu, 2) with w-stacking; weight sum (1,))."""
+        raise NotImplementedError
+
+    def mark_clean(self) -> None:
+        """Pass A has consumed every strip row and the halo rows were zeroed."""
+        raise NotImplementedError
+
+    def pass_rows(self, grid, y0: int, y1: int, plane: int = 0):
+        """Pass A over rows [y0, y1) of one plane's buffer -> H (npix_x / 4, y1 - y0, 4, 2); zeroes the rows."""
+        raise NotImplementedError
+
+    def pass_cols(self, H, i0: int, i1: int, norm=None):
+        """Pass B + crop + grid correction (/ norm) of image rows [i0, i1) from H ((i1 - i0) / 4, nv, 4, 2)."""
+        raise NotImplementedError
+
+    def pass_cols_wplane(self, H, i0: int, i1: int, plane: int, first: bool, acc):
+        """Pass B of one w plane with its w screen, added into acc (overwritten when `first`)."""
+        raise NotImplementedError
+
+    def finish_rows(self, acc, i0: int, i1: int, norm=None):
+        """The final w and grid corrections of image rows [i0, i1) (acc, in place), / norm."""
+        raise NotImplementedError
+
+    def live_rows(self, h: int, plane: int = 0):
+        """Bool over buffer rows [0, h) of `plane`: the rows that may hold a
+        non-zero cell, when the backend knows them before pass A; None: it
+        does not (the driver then scans pass A's output)."""
+        return None
+
+    def pass_rows_packed(self, grid, y0: int, y1: int, live, count: int, plane: int = 0):
+        """Pass A keeping only the live rows (`live`: bool over [y0, y1) with
+        `count` Trues) -> (npix_x / 4, count, 4, 2), the sparse all-to-all's
+        send buffer. Default: packed after a dense pass A."""
+        return _pack_live(self.pass_rows(grid, y0, y1, plane), live, count)
+
+    def planes(self, buf):
+        """The buffer of `grid_strip` as (nplanes, nrows, nu, 2): a view (2-D is the one-plane case)."""
+        return buf[None] if self.nplanes == 1 else buf
+
+    def wire(self, H):
+        """Pass-A blocks as they cross the all-to-all: complex64 for the packed
+        class (its own precision; half the bytes), complex128 otherwise."""
+        return H.to(torch.float32) if self.single else H
+
+
+_ADOPTED: dict = {}
+
+
+def _adopt(backend) -> StripBackend:
+    """`backend` as a StripBackend. The drivers used to take any object with
+    the stages (and whichever optional members it chose to define); such an
+    object keeps working: its class is given StripBackend as a last base, so
+    what it defines stands and what it leaves out falls to the defaults."""
+    if not isinstance(backend, StripBackend):
+        cls = type(backend)
+        if cls not in _ADOPTED:
+            _ADOPTED[cls] = type(cls.__name__, (cls, StripBackend), {})
+        backend.__class__ = _ADOPTED[cls]
+    return backend
+
+
+class HipStripBackend(StripBackend):
     """Per-rank stages on the current GPU through libcip_hip.so:
     cip_grid_tiles_strip (accumulating gridder) onto a buffer holding only the
     rank's strip + halo rows (`bind`: 1/N of the grid plus W - 1 rows instead
@@ -382,13 +469,10 @@ class HipStripBackend:
             self.dirty = False
 
     def spawn(self) -> "HipStripBackend":
-        """A backend of the same configuration (another rank's, for the
-        single-process emulation)."""
         return HipStripBackend(self.params, self.px, self.py, self.npix_x, self.npix_y, device=self.device,
                                rows=self.rows, single_precision_accumulation=self.single)
 
     def bind(self, layout: StripLayout, rank: int) -> "HipStripBackend":
-        """Hold rank `rank`'s strip + halo rows of `layout` (reallocates when they change)."""
         self._alloc(strip_buffer_rows(layout, rank))
         return self
 
@@ -419,7 +503,6 @@ class HipStripBackend:
         return self.grid, sumw
 
     def mark_clean(self) -> None:
-        """Pass A consumed the strip rows and the halo rows were zeroed."""
         self.dirty = False
 
     def pass_rows(self, grid, y0: int, y1: int, plane: int = 0):
@@ -440,7 +523,7 @@ class HipStripBackend:
         count, 4, 2): the sparse all-to-all's send buffer, written by pass A
         itself (cip_strip_rows_packed) instead of packed after it."""
         if not (self._bits_valid and self.dirty):
-            return _pack_live(self.pass_rows(grid, y0, y1, plane), live, count)
+            return super().pass_rows_packed(grid, y0, y1, live, count, plane)
         slot = torch.cumsum(live.to(torch.int64), 0).sub_(1)
         slot = torch.where(live, slot, torch.full_like(slot, -1))
         H = torch.empty((self.npix_x // COL_BLOCK, count, COL_BLOCK, 2), dtype=torch.float64, device=self.device)
@@ -474,148 +557,21 @@ class HipStripBackend:
         return acc
 
     def finish_rows(self, acc, i0: int, i1: int, norm=None):
-        """The final w and grid corrections of image rows [i0, i1) (acc, in place), / norm."""
         call(self.device, "cip_strip_wfinal", acc, self.params, self.npix_x, self.npix_y, self.px, self.py, int(i0),
              int(i1), norm, STREAM)
         return acc
 
 
-def _assemble_H(pieces: Sequence, nb: int, layout: StripLayout, device, dtype, idx=None):
-    """Rank s's pass-B input from every rank's pass-A blocks [i0_s / 4, i1_s / 4)
-    (piece r: (nb, h_r, 4, 2), or with idx[r] (sparse) only rank r's rows
-    idx[r] of its strip: (nb, len(idx[r]), 4, 2), the other rows zero) ->
-    (nb, nv, 4, 2). The torch form, for CPU tensors (the gloo tests' backend);
-    GPU buffers go through _unpack_rows (one copy kernel)."""
-    sparse = idx is not None and any(i is not None for i in idx)
-    H = (torch.zeros if sparse else torch.empty)((nb, layout.nv, COL_BLOCK, 2), dtype=dtype, device=device)
-    for r, piece in enumerate(pieces):
-        y0, y1 = layout.rows(r)
-        if idx is None or idx[r] is None:
-            H[:, y0:y1] = piece.reshape(nb, y1 - y0, COL_BLOCK, 2)
-        elif idx[r].numel():
-            H[:, y0 + idx[r]] = piece.reshape(nb, idx[r].numel(), COL_BLOCK, 2)
-    return H
-
-
-def invert_strips(data: StripData, freq, layout: StripLayout, backend, *, dst: int = 0, group=None,
-                  stages: Optional[dict] = None, sparse: bool = True, gather_async: bool = False):
-    """This rank's share of the strip-distributed invert (torch.distributed
-    initialised, one rank per strip). Returns the normalised dirty image
-    (npix_x, npix_y) on `dst`, None elsewhere. Collectives: one point-to-point
-    halo exchange with the ring neighbours, one all-to-all of the pass-A
-    blocks, a scalar all-reduce of the weight sum, a gather of image rows.
-    The backend is bound to this rank's strip + halo rows (`strip_buffer_rows`).
-    `sparse` (default): the all-to-all carries only the rows of the pass-A
-    output that can be non-zero (after an all-gather of the live-row masks).
-    `gather_async`: return a `PendingGather` at once (the image-row gather in
-    flight on the communicator's stream, e.g. beside the next invert's
-    gridding); `.wait()` gives the image.
-    `stages` (a dict, diagnostic): each stage is synchronised and its seconds
-    added under its name (grid, halo, rows, alltoall, cols, gather), and the
-    all-to-all's bytes sent by this rank under a2a_send_bytes."""
-    import time  # pylint: disable=import-outside-toplevel
-
+def _dist():
+    """torch.distributed, imported on first use (its entry points are looked up per call)."""
     import torch.distributed as dist  # pylint: disable=import-outside-toplevel
 
-    t_last = [time.perf_counter()]
-    single = not dist.is_available() or not dist.is_initialized()
-    world = 1 if single else dist.get_world_size(group)
-    rank = 0 if single else dist.get_rank(group)
-    if world != layout.world:
-        raise ValueError("the layout was planned for another number of ranks")
-    backend.bind(layout, rank)
-    y0, y1 = layout.rows(rank)
-    h = y1 - y0
-    buf, sumw = backend.grid_strip(data, freq)
-
-    def mark(name):
-        if stages is not None:
-            if buf.is_cuda:
-                torch.cuda.synchronize(buf.device)
-            t = time.perf_counter()
-            stages[name] = stages.get(name, 0.0) + t - t_last[0]
-            t_last[0] = t
-
-    mark("grid")
-    # w-stacking buffers hold every plane's rows: rows are the second axis
-    nplanes = int(getattr(backend, "nplanes", 1))
-    rowsel = (lambda a, b: buf[a:b]) if nplanes == 1 else (lambda a, b: buf[:, a:b])
-    if world > 1:
-        # halo: buffer rows [h, h + W - 1) = the grid rows past the strip ->
-        # the next rank, added to its first rows (every plane's at once)
-        send = rowsel(h, h + layout.halo).contiguous()
-        recv = torch.empty_like(send)
-        ops = [dist.P2POp(dist.isend, send, (rank + 1) % world, group),
-               dist.P2POp(dist.irecv, recv, (rank - 1) % world, group)]
-        for w in dist.batch_isend_irecv(ops):
-            w.wait()
-        rowsel(h, h + layout.halo).zero_()
-        rowsel(0, layout.halo).add_(recv)
-        dist.all_reduce(sumw, group=group)
-    mark("halo")
-    if nplanes > 1:
-        # per w plane: pass A on this rank's rows, the all-to-all, pass B with
-        # the plane's w screen added into this rank's image rows
-        i0, i1 = layout.image_rows(rank)
-        acc = torch.empty((i1 - i0, backend.npix_y), dtype=torch.float64, device=buf.device)
-        for p in range(nplanes):
-            snd = _packed_send(backend, buf[p], h, p, layout, rank, world, group) if (sparse and world > 1) else None
-            if snd is not None:
-                mark("rows")
-                Hm = _alltoall_rows(snd[0], layout, rank, world, group, snd[1], snd[2], snd[3],
-                                    stages).to(torch.float64)
-            else:
-                H = backend.pass_rows(buf[p], 0, h, plane=p)
-                mark("rows")
-                Hm = (_alltoall_H(_wire(H, backend), layout, rank, world, group,
-                                  live=_live_of(backend, H, h, p) if sparse else None, stats=stages).to(torch.float64)
-                      if world > 1 else H)
-            mark("alltoall")
-            backend.pass_cols_wplane(Hm, i0, i1, p, p == 0, acc)
-            mark("cols")
-        backend.mark_clean()
-        rows_img = backend.finish_rows(acc, i0, i1, norm=sumw)
-        mark("final")
-        return _gather_rows(rows_img, layout, rank, world, dst, group, mark, async_op=gather_async)
-    snd = _packed_send(backend, buf, h, 0, layout, rank, world, group) if (sparse and world > 1) else None
-    i0, i1 = layout.image_rows(rank)
-    if snd is not None:
-        backend.mark_clean()
-        mark("rows")
-        Hm = _alltoall_rows(snd[0], layout, rank, world, group, snd[1], snd[2], snd[3], stages).to(torch.float64)
-    else:
-        H = backend.pass_rows(buf, 0, h)
-        live = _live_of(backend, H, h) if (sparse and world > 1) else None
-        backend.mark_clean()
-        mark("rows")
-        Hm = (_alltoall_H(_wire(H, backend), layout, rank, world, group, live=live, stats=stages).to(torch.float64)
-              if world > 1 else H)
-    mark("alltoall")
-    rows_img = backend.pass_cols(Hm, i0, i1, norm=sumw)
-    mark("cols")
-    return _gather_rows(rows_img, layout, rank, world, dst, group, mark, async_op=gather_async)
+    return dist
 
 
-def _wire(H, backend):
-    """The pass-A blocks as they cross the all-to-all: complex64 for the packed
-    class (its own precision; half the bytes), complex128 otherwise."""
-    return H.to(torch.float32) if getattr(backend, "single", False) else H
-
-
-def _live_of(backend, H, h: int, plane: int = 0):
-    """Rows of this rank's pass-A output H (nb, h, 4, 2) that can be non-zero:
-    the backend's dirty-tile rows when it knows them, else a scan of H (a
-    row whose grid row was empty transforms to exact zeros either way)."""
-    fn = getattr(backend, "live_rows", None)
-    live = fn(h, plane) if fn is not None else None
-    if live is None:
-        live = (H != 0).reshape(H.shape[0], h, -1).any(dim=2).any(dim=0)
-    return live.to(torch.bool)
-
-
-def _elem_bytes(H) -> int:
-    """Bytes of one complex element of a (..., 2) real view."""
-    return 2 * H.element_size()
+def _heights(layout: StripLayout) -> list:
+    """Every rank's strip height (grid rows)."""
+    return [layout.rows(r)[1] - layout.rows(r)[0] for r in range(layout.world)]
 
 
 def _pack_live(H, live, count: int):
@@ -630,7 +586,7 @@ def _pack_live(H, live, count: int):
     slot = torch.cumsum(live.to(torch.int64), 0).sub_(1)
     slot = torch.where(live, slot, torch.full_like(slot, -1))
     out = torch.empty((nb, count) + tuple(H.shape[2:]), dtype=H.dtype, device=H.device)
-    call(H.device, "cip_strip_pack_rows", H, nb, h, _elem_bytes(H), slot, count, STREAM, out)
+    call(H.device, "cip_strip_pack_rows", H, nb, h, 2 * H.element_size(), slot, count, STREAM, out)
     return out
 
 
@@ -647,7 +603,7 @@ def _unpack_rows(recv, nb: int, layout: StripLayout, masks, dtype, stacked=None)
     tensor, when the caller has it)."""
     dev = recv.device
     nv, world = layout.nv, layout.world
-    hs = [layout.rows(r)[1] - layout.rows(r)[0] for r in range(world)]
+    hs = _heights(layout)
     if stacked is None:
         stacked = torch.zeros((world, max(hs)), dtype=torch.uint8, device=dev)
         for r, m in enumerate(masks):
@@ -673,73 +629,35 @@ def _unpack_rows(recv, nb: int, layout: StripLayout, masks, dtype, stacked=None)
     return H
 
 
-def _exchange_masks(live, layout: StripLayout, rank: int, world: int, group):
-    """All ranks' live-row masks of their pass-A output (one all-gather) ->
-    (stacked (world, max rows) uint8, counts, masks (bool over each rank's
-    rows)); the counts are the all-to-all's split sizes (one host wait)."""
-    import torch.distributed as dist  # pylint: disable=import-outside-toplevel
+def _assemble_H(recv, nb: int, layout: StripLayout, counts, masks):
+    """_unpack_rows in torch index form, for CPU tensors (the gloo tests'
+    backend): rank r's piece of `recv` is (nb, counts[r], 4, 2)."""
+    sparse = any(m is not None for m in masks)
+    H = (torch.zeros if sparse else torch.empty)((nb, layout.nv, COL_BLOCK, 2), dtype=recv.dtype, device=recv.device)
+    for r, piece in enumerate(torch.split(recv, [nb * c * COL_BLOCK * 2 for c in counts])):
+        y0, y1 = layout.rows(r)
+        if masks[r] is None:
+            H[:, y0:y1] = piece.reshape(nb, y1 - y0, COL_BLOCK, 2)
+        elif counts[r]:
+            H[:, y0 + torch.nonzero(masks[r]).reshape(-1)] = piece.reshape(nb, counts[r], COL_BLOCK, 2)
+    return H
 
-    hs = [layout.rows(r)[1] - layout.rows(r)[0] for r in range(world)]
-    h = hs[rank]
-    mine = torch.zeros(max(hs), dtype=torch.uint8, device=live.device)
-    mine[:h] = live.to(torch.uint8)
-    allm = [torch.empty_like(mine) for _ in range(world)]
-    dist.all_gather(allm, mine, group=group)
-    stacked = torch.stack(allm)
+
+def _stack_masks(lives: Sequence, layout: StripLayout, allgather=None):
+    """The ranks' live-row masks (`lives`, bool over each one's strip rows;
+    with `allgather` this rank's only, the others' fetched by it) -> (stacked
+    (world, max rows) uint8, counts, masks (bool per rank)); the counts are the
+    all-to-all's split sizes (the one host wait)."""
+    hs = _heights(layout)
+    padded = []
+    for live in lives:
+        padded.append(torch.zeros(max(hs), dtype=torch.uint8, device=live.device))
+        padded[-1][:live.shape[0]] = live.to(torch.uint8)
+    if allgather is not None:
+        padded = allgather(padded[0])
+    stacked = torch.stack(padded)
     counts = [int(c) for c in stacked.sum(dim=1).tolist()]
-    return stacked, counts, [allm[r][:hs[r]].to(torch.bool) for r in range(world)]
-
-
-def _alltoall_rows(Hsend, layout: StripLayout, rank: int, world: int, group, counts, masks, stacked=None,
-                   stats: Optional[dict] = None):
-    """The all-to-all of pass-A rows: `Hsend` (nb_all, counts[rank], 4, 2) is
-    this rank's send buffer (its live rows, or every row when masks[rank] is
-    None); rank s receives blocks [i0_s / 4, i1_s / 4) of every rank's rows ->
-    its pass-B input (nb, nv, 4, 2), rows nobody sent zero."""
-    import torch.distributed as dist  # pylint: disable=import-outside-toplevel
-
-    i0, i1 = layout.image_rows(rank)
-    nb = (i1 - i0) // COL_BLOCK
-    splits_in = [(layout.image_rows(s)[1] - layout.image_rows(s)[0]) // COL_BLOCK * counts[rank] * COL_BLOCK * 2
-                 for s in range(world)]
-    splits_out = [nb * counts[r] * COL_BLOCK * 2 for r in range(world)]
-    if stats is not None:
-        stats["a2a_send_bytes"] = stats.get("a2a_send_bytes", 0) + sum(splits_in) * Hsend.element_size()
-    recv = torch.empty(sum(splits_out), dtype=Hsend.dtype, device=Hsend.device)
-    dist.all_to_all_single(recv, Hsend.reshape(-1), splits_out, splits_in, group=group)
-    if Hsend.device.type == "cuda":
-        return _unpack_rows(recv, nb, layout, masks, Hsend.dtype, stacked)
-    pieces = list(torch.split(recv, splits_out))
-    idx = [None if m is None else torch.nonzero(m).reshape(-1) for m in masks]
-    return _assemble_H(pieces, nb, layout, Hsend.device, Hsend.dtype, idx)
-
-
-def _alltoall_H(H, layout: StripLayout, rank: int, world: int, group, live=None, stats: Optional[dict] = None):
-    """The all-to-all of pass-A blocks: rank s receives blocks [i0_s / 4,
-    i1_s / 4) of every rank's rows -> its pass-B input (nb, nv, 4, 2).
-    Sparse (`live`, this rank's rows that can be non-zero): the ranks first
-    all-gather their live-row masks, then send only live rows; a receiver
-    fills the others with zeros. The tall edge strips of C4's cost-balanced
-    layout are mostly empty long-baseline rows."""
-    if live is None:
-        hs = [layout.rows(r)[1] - layout.rows(r)[0] for r in range(world)]
-        return _alltoall_rows(H, layout, rank, world, group, hs, [None] * world, stats=stats)
-    stacked, counts, masks = _exchange_masks(live, layout, rank, world, group)
-    return _alltoall_rows(_pack_live(H, masks[rank], counts[rank]), layout, rank, world, group, counts, masks,
-                          stacked, stats)
-
-
-def _packed_send(backend, buf, h: int, plane: int, layout: StripLayout, rank: int, world: int, group):
-    """Sparse exchange with pass A writing the send buffer (the backend knows
-    its live rows before pass A): (Hsend on the wire, counts, masks, stacked),
-    or None when it does not (then pass A runs dense and _alltoall_H packs)."""
-    fn = getattr(backend, "live_rows", None)
-    live = fn(h, plane) if fn is not None else None
-    if live is None or not hasattr(backend, "pass_rows_packed"):
-        return None
-    stacked, counts, masks = _exchange_masks(live, layout, rank, world, group)
-    Hs = backend.pass_rows_packed(buf, 0, h, masks[rank], counts[rank], plane=plane)
-    return _wire(Hs, backend), counts, masks, stacked
+    return stacked, counts, [padded[r][:hs[r]].to(torch.bool) for r in range(layout.world)]
 
 
 class PendingGather:
@@ -752,11 +670,12 @@ class PendingGather:
     def __init__(self, work, gathered, layout: StripLayout, rank: int, dst: int, image=None):
         self._work, self._gathered, self._layout = work, gathered, layout
         self._rank, self._dst, self._image = rank, dst, image
-        self._done = work is None
+        self._done = work is None and gathered is None
 
     def wait(self):
         if not self._done:
-            self._work.wait()
+            if self._work is not None:  # None: the gather was a blocking one
+                self._work.wait()
             self._done = True
             if self._rank == self._dst:
                 lay = self._layout
@@ -766,206 +685,282 @@ class PendingGather:
         return self._image
 
 
-def _gather_rows(rows_img, layout: StripLayout, rank: int, world: int, dst: int, group, mark,
-                 async_op: bool = False):
-    """This rank's image rows -> the whole image on `dst` (None elsewhere);
-    async_op: a PendingGather instead."""
-    import torch.distributed as dist  # pylint: disable=import-outside-toplevel
+class _DistExchange:
+    """The strip invert's exchanges as torch.distributed collectives (RCCL, or
+    gloo on CPU tensors): this process holds one rank, `mine` = [rank]. Every
+    operation takes and returns one entry per rank in `mine`."""
 
-    if world == 1:
-        return PendingGather(None, None, layout, rank, dst, rows_img) if async_op else rows_img
-    # gather the image rows (strips padded to the largest: gather needs equal sizes)
-    hmax = max(layout.image_rows(r)[1] - layout.image_rows(r)[0] for r in range(world))
-    if rows_img.shape[0] < hmax:
-        rows_img = torch.cat([rows_img, rows_img.new_zeros((hmax - rows_img.shape[0], rows_img.shape[1]))])
-    gathered = [torch.empty_like(rows_img) for _ in range(world)] if rank == dst else None
-    work = dist.gather(rows_img, gathered, dst=dst, group=group, async_op=async_op)
-    if async_op:
-        return PendingGather(work, gathered, layout, rank, dst)
-    mark("gather")
-    if rank != dst:
-        return None
-    return torch.cat([g[:layout.image_rows(r)[1] - layout.image_rows(r)[0]] for r, g in enumerate(gathered)])
+    def __init__(self, layout: StripLayout, group, dst: int, gather_async: bool):
+        dist = _dist()
+        alone = not dist.is_available() or not dist.is_initialized()
+        self.world = 1 if alone else dist.get_world_size(group)
+        self.rank = 0 if alone else dist.get_rank(group)
+        self.mine = [self.rank]
+        self.layout, self.group, self.dst, self.gather_async = layout, group, dst, gather_async
+        # diagnostic stage names: the live-row scan of pass A's output counts as
+        # "rows", packing and unpacking as this rank's "alltoall"; the gather is
+        # timed only where the rank waits for it
+        self.stage_names = {"scan": "rows", "pack": "alltoall", "assemble": "alltoall",
+                            "gather": "gather" if self.world > 1 and not gather_async else None}
 
+    def halo(self, tails):
+        """Send the halo rows to rank + 1 -> [those of rank - 1]."""
+        dist = _dist()
+        send = tails[0].contiguous()
+        recv = torch.empty_like(send)
+        ops = [dist.P2POp(dist.isend, send, (self.rank + 1) % self.world, self.group),
+               dist.P2POp(dist.irecv, recv, (self.rank - 1) % self.world, self.group)]
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+        return [recv]
 
-def _count_a2a(stages, Hs, lives, layout: StripLayout, backend):
-    """Add each rank's all-to-all send bytes (to the other ranks) to its
-    stage dict: (N - 1) / N of its (live) pass-A rows on the wire."""
-    if stages is None or layout.world == 1:
-        return
-    esize = _wire(Hs[0][:0], backend).element_size()
-    for r, H in enumerate(Hs):
-        rows = int(lives[r].sum()) if lives is not None else H.shape[1]
-        i0, i1 = layout.image_rows(r)
-        own = (i1 - i0) // COL_BLOCK
-        stages[r]["a2a_send_bytes"] = stages[r].get("a2a_send_bytes", 0) + \
-            (H.shape[0] - own) * rows * COL_BLOCK * 2 * esize
+    def sum_weights(self, sums):
+        _dist().all_reduce(sums[0], group=self.group)
+        return sums[0]
 
+    def live_masks(self, lives):
+        def allgather(mine):
+            allm = [torch.empty_like(mine) for _ in range(self.world)]
+            _dist().all_gather(allm, mine, group=self.group)
+            return allm
 
-def _local_pieces(Hs, b0: int, b1: int, backend, lives):
-    """The emulated all-to-all for one receiver: blocks [b0, b1) of every
-    rank's H, only its live rows when `lives` (sparse) - as _alltoall_H
-    sends them."""
-    if lives is None:
-        return [_wire(H[b0:b1], backend) for H in Hs], None
-    idx = [torch.nonzero(lv).reshape(-1) for lv in lives]
-    return [_wire(H[b0:b1].index_select(1, i), backend) for H, i in zip(Hs, idx)], idx
+        return _stack_masks(lives, self.layout, allgather)
 
+    def alltoall(self, i: int, sends, counts):
+        """Rank s receives blocks [i0_s / 4, i1_s / 4) of every rank's sent rows -> the flat receive buffer."""
+        nbs = [(b - a) // COL_BLOCK for a, b in zip(self.layout.x_bounds, self.layout.x_bounds[1:])]
+        splits_in = [nb * counts[self.rank] * COL_BLOCK * 2 for nb in nbs]
+        splits_out = [nbs[self.rank] * c * COL_BLOCK * 2 for c in counts]
+        recv = torch.empty(sum(splits_out), dtype=sends[i].dtype, device=sends[i].device)
+        _dist().all_to_all_single(recv, sends[i].reshape(-1), splits_out, splits_in, group=self.group)
+        return recv
 
-def _local_sends(Hs, lives, backend, timed):
-    """The emulated all-to-all's send side: every rank packs its live rows
-    once (timed as its "pack" stage, as _alltoall_H's sender does) ->
-    (sends, masks, counts, stacked masks); a receiver's buffer is the concatenation of the
-    sends' block ranges (the network: untimed), unpacked by _unpack_rows."""
-    wires = [_wire(H, backend) for H in Hs]
-    hs = [int(H.shape[1]) for H in Hs]
-    if lives is None:
-        return wires, [None] * len(Hs), hs, None
-    masks = [lv.to(torch.bool) for lv in lives]
-    counts = [int(c) for c in torch.stack([m.sum() for m in masks]).tolist()]
-    stacked = torch.zeros((len(Hs), max(hs)), dtype=torch.uint8, device=Hs[0].device)
-    for r, m in enumerate(masks):
-        stacked[r, :hs[r]] = m.to(torch.uint8)
-    sends = [timed(r, "pack", lambda r=r: _pack_live(wires[r], masks[r], counts[r])) for r in range(len(Hs))]
-    return sends, masks, counts, stacked
+    def sent_bytes(self, i: int, send) -> int:
+        """The bytes handed to the all-to-all."""
+        return send.numel() * send.element_size()
 
-
-def _local_pass_a(ranks, grids, hs, plane, sparse: bool, on_gpu: bool, timed, backend, layout, stages):
-    """Every rank's pass A in the emulation -> (Hs, lives, sends): with the
-    sparse exchange on the GPU and every rank's live rows known from its mask,
-    pass A writes the packed send buffer itself (Hs None; sends = (buffers,
-    masks, counts, stacked)), else dense pass A (sends from _local_sends)."""
-    world = len(ranks)
-    if sparse and world > 1 and on_gpu and all(hasattr(rk, "pass_rows_packed") for rk in ranks):
-        lives = [rk.live_rows(h, plane) for rk, h in zip(ranks, hs)]
-        if all(lv is not None for lv in lives):
-            masks = [lv.to(torch.bool) for lv in lives]
-            counts = [int(c) for c in torch.stack([m.sum() for m in masks]).tolist()]
-            stacked = torch.zeros((world, max(hs)), dtype=torch.uint8, device=masks[0].device)
-            for r, m in enumerate(masks):
-                stacked[r, :hs[r]] = m.to(torch.uint8)
-            bufs = [timed(r, "rows", lambda r=r: _wire(ranks[r].pass_rows_packed(
-                grids[r], 0, hs[r], masks[r], counts[r], plane=plane), backend)) for r in range(world)]
-            _count_a2a(stages, bufs, masks, layout, backend)
-            return None, masks, (bufs, masks, counts, stacked)
-    Hs = [timed(r, "rows", lambda r=r: ranks[r].pass_rows(grids[r], 0, hs[r], plane=plane)) for r in range(world)]
-    lives = [_live_of(ranks[r], Hs[r], hs[r], plane) for r in range(world)] if (sparse and world > 1) else None
-    _count_a2a(stages, Hs, lives, layout, backend)
-    sends = _local_sends(Hs, lives, backend, timed) if (world > 1 and on_gpu) else None
-    return Hs, lives, sends
+    def gather(self, rows_imgs):
+        """This rank's image rows -> the whole image on `dst` (None elsewhere); gather_async: a PendingGather."""
+        rows_img, layout, rank, dst = rows_imgs[0], self.layout, self.rank, self.dst
+        if self.world == 1:
+            return PendingGather(None, None, layout, rank, dst, rows_img) if self.gather_async else rows_img
+        # strips padded to the largest: gather needs equal sizes
+        hmax = max(b - a for a, b in zip(layout.x_bounds, layout.x_bounds[1:]))
+        if rows_img.shape[0] < hmax:
+            rows_img = torch.cat([rows_img, rows_img.new_zeros((hmax - rows_img.shape[0], rows_img.shape[1]))])
+        gathered = [torch.empty_like(rows_img) for _ in range(self.world)] if rank == dst else None
+        work = _dist().gather(rows_img, gathered, dst=dst, group=self.group, async_op=self.gather_async)
+        pending = PendingGather(work, gathered, layout, rank, dst)
+        return pending if self.gather_async else pending.wait()
 
 
-def invert_strips_local(datas: Sequence[StripData], freq, layout: StripLayout, backend,
+class _LocalExchange:
+    """The same exchanges in memory: every rank is in this process (one
+    device), `mine` = all of them; the network's part is untimed."""
+
+    def __init__(self, layout: StripLayout):
+        self.layout, self.world = layout, layout.world
+        self.mine = list(range(self.world))
+        self.stage_names = {"scan": None, "gather": None}
+
+    def halo(self, tails):
+        sent = [t.clone() for t in tails]
+        return [sent[(r - 1) % self.world] for r in self.mine]
+
+    def sum_weights(self, sums):
+        sumw = sums[0].clone()
+        for sw in sums[1:]:
+            sumw = sumw + sw
+        return sumw
+
+    def live_masks(self, lives):
+        return _stack_masks(lives, self.layout)
+
+    def alltoall(self, i: int, sends, counts):  # pylint: disable=unused-argument
+        i0, i1 = self.layout.image_rows(i)
+        return torch.cat([snd[i0 // COL_BLOCK:i1 // COL_BLOCK].reshape(-1) for snd in sends])
+
+    def sent_bytes(self, i: int, send) -> int:
+        """The bytes bound for the other N - 1 ranks."""
+        i0, i1 = self.layout.image_rows(i)
+        return (send.numel() - send[i0 // COL_BLOCK:i1 // COL_BLOCK].numel()) * send.element_size()
+
+    def gather(self, rows_imgs):
+        return torch.cat(rows_imgs, dim=0)
+
+
+class _Clock:
+    """The diagnostic stage times: `clock(i, name, fn)` runs fn() and, with
+    `stages` (one dict per rank in the process), adds its synchronised seconds
+    to stages[i][name]. `laps` (the distributed driver): a stage lasts from the
+    end of the one before it, so whatever runs between two of them - the
+    collectives - counts with the later. Without `stages` it only calls fn."""
+
+    def __init__(self, stages, device, laps: bool, names: dict):
+        self.stages, self.laps, self.names = stages, laps, names
+        self.device = device if device is not None and torch.device(device).type == "cuda" else None
+        self.last = time.perf_counter()
+
+    def _now(self) -> float:
+        if self.device is not None:
+            torch.cuda.synchronize(self.device)
+        return time.perf_counter()
+
+    def __call__(self, i: int, name: str, fn):
+        if self.stages is None:
+            return fn()
+        t0 = self.last if self.laps else self._now()
+        out = fn()
+        self.last = self._now()
+        self.add(i, self.names.get(name, name), self.last - t0)
+        return out
+
+    def add(self, i: int, name, amount) -> None:
+        if self.stages is not None and name is not None:
+            self.stages[i][name] = self.stages[i].get(name, 0) + amount
+
+    def idle(self, i: int, name: str) -> None:
+        """A stage with nothing to do (one strip): laps still report it."""
+        if self.laps:
+            self(i, name, lambda: None)
+
+
+def _pass_a(ranks, grids, plane: int, last: bool, ex, clock: _Clock, sparse: bool):
+    """Pass A of one plane on every rank in the process -> (sends, counts,
+    masks, stacked): sends[i] is rank ex.mine[i]'s all-to-all send buffer
+    (npix_x / 4, counts[r], 4, 2) on the wire. A sparse exchange sends only
+    the rows that can be non-zero (masks[r]; a row whose grid row was empty
+    transforms to exact zeros): a backend that knows them before pass A has it
+    write the packed buffer; otherwise pass A runs dense, its output is
+    scanned and packed. Dense: every row (masks None). One strip: pass A's
+    output as it is. The `last` plane's pass A leaves the buffer clean."""
+    hs = _heights(ex.layout)
+
+    def run(i, fn):
+        H = clock(i, "rows", fn)
+        if last:
+            ranks[i].mark_clean()
+        return H
+
+    sparse = sparse and ex.world > 1
+    known = [ranks[i].live_rows(hs[r], plane) if sparse else None for i, r in enumerate(ex.mine)]
+    Hs = [run(i, lambda: ranks[i].pass_rows(grids[i], 0, hs[r], plane=plane)) if known[i] is None else None
+          for i, r in enumerate(ex.mine)]
+    if ex.world == 1:
+        return Hs, None, None, None
+    if not sparse:
+        return [ranks[i].wire(H) for i, H in enumerate(Hs)], hs, [None] * ex.world, None
+    lives = [lv if H is None else clock(i, "scan", lambda: (H != 0).reshape(H.shape[0], H.shape[1], -1).any(dim=2)
+                                        .any(dim=0)) for i, (H, lv) in enumerate(zip(Hs, known))]
+    stacked, counts, masks = ex.live_masks([lv.to(torch.bool) for lv in lives])
+    sends = []
+    for i, r in enumerate(ex.mine):
+        if Hs[i] is None:
+            sends.append(run(i, lambda: ranks[i].wire(
+                ranks[i].pass_rows_packed(grids[i], 0, hs[r], masks[r], counts[r], plane=plane))))
+        else:
+            H = ranks[i].wire(Hs[i])
+            sends.append(clock(i, "pack", lambda: _pack_live(H, masks[r], counts[r])))
+    return sends, counts, masks, stacked
+
+
+def _invert(datas, freq, layout: StripLayout, ranks, ex, clock: _Clock, sparse: bool):
+    """The strip invert of the ranks in this process: ranks[i] is the bound
+    backend of rank ex.mine[i], datas[i] its strip, `ex` the exchange between
+    all ranks. 2-D is the one-plane case of w-stacking; only pass B differs
+    (pass_cols with the norm; pass_cols_wplane per plane, then finish_rows)."""
+    world, mine = ex.world, ex.mine
+    local = range(len(mine))
+    hs = _heights(layout)
+    grids, sums = [None] * len(mine), [None] * len(mine)
+    for i in local:
+        buf, sums[i] = clock(i, "grid", lambda: ranks[i].grid_strip(datas[i], freq))
+        grids[i] = ranks[i].planes(buf)
+    nplanes = int(grids[0].shape[0])
+    sumw = sums[0]
+    if world > 1:
+        # halo: buffer rows [h, h + W - 1) = the grid rows past the strip ->
+        # the next rank, added to its first rows (every plane's at once)
+        tails = [grids[i][:, hs[r]:hs[r] + layout.halo] for i, r in enumerate(mine)]
+        heads = ex.halo(tails)
+        sumw = ex.sum_weights(sums)
+        for tail in tails:
+            tail.zero_()
+        for i in local:
+            clock(i, "halo", lambda: grids[i][:, :layout.halo].add_(heads[i]))
+    else:
+        clock.idle(0, "halo")
+    rows = [layout.image_rows(r) for r in mine]
+    outs = [None if nplanes == 1 else torch.empty((i1 - i0, ranks[i].npix_y), dtype=torch.float64,
+                                                  device=grids[i].device) for i, (i0, i1) in enumerate(rows)]
+    for p in range(nplanes):
+        sends, counts, masks, stacked = _pass_a(ranks, [g[p] for g in grids], p, p == nplanes - 1, ex, clock, sparse)
+        for i, (i0, i1) in enumerate(rows):
+            if world > 1:
+                clock.add(i, "a2a_send_bytes", ex.sent_bytes(i, sends[i]))
+                recv, nb = ex.alltoall(i, sends, counts), (i1 - i0) // COL_BLOCK
+                Hm = clock(i, "assemble", lambda: (
+                    _unpack_rows(recv, nb, layout, masks, recv.dtype, stacked) if recv.is_cuda else
+                    _assemble_H(recv, nb, layout, counts, masks)).to(torch.float64))
+            else:
+                Hm = sends[i]
+                clock.idle(i, "alltoall")
+            if nplanes == 1:
+                outs[i] = clock(i, "cols", lambda: ranks[i].pass_cols(Hm, i0, i1, norm=sumw))
+            else:
+                clock(i, "cols", lambda: ranks[i].pass_cols_wplane(Hm, i0, i1, p, p == 0, outs[i]))
+    if nplanes > 1:
+        for i, (i0, i1) in enumerate(rows):
+            clock(i, "final", lambda: ranks[i].finish_rows(outs[i], i0, i1, norm=sumw))
+    return clock(0, "gather", lambda: ex.gather(outs))
+
+
+def invert_strips(data: StripData, freq, layout: StripLayout, backend: StripBackend, *, dst: int = 0, group=None,
+                  stages: Optional[dict] = None, sparse: bool = True, gather_async: bool = False):
+    """This rank's share of the strip-distributed invert (torch.distributed
+    initialised, one rank per strip). Returns the normalised dirty image
+    (npix_x, npix_y) on `dst`, None elsewhere. Collectives: one point-to-point
+    halo exchange with the ring neighbours, one all-to-all of the pass-A
+    blocks, a scalar all-reduce of the weight sum, a gather of image rows.
+    The backend is bound to this rank's strip + halo rows (`strip_buffer_rows`).
+    `sparse` (default): the all-to-all carries only the rows of the pass-A
+    output that can be non-zero (after an all-gather of the live-row masks).
+    `gather_async`: return a `PendingGather` at once (the image-row gather in
+    flight on the communicator's stream, e.g. beside the next invert's
+    gridding); `.wait()` gives the image.
+    `stages` (a dict, diagnostic): each stage is synchronised and its seconds
+    added under its name (grid, halo, rows, alltoall, cols, final, gather), and
+    the all-to-all's bytes sent by this rank under a2a_send_bytes."""
+    backend = _adopt(backend)
+    ex = _DistExchange(layout, group, dst, gather_async)
+    clock = _Clock(None if stages is None else [stages], backend.device, True, ex.stage_names)
+    if ex.world != layout.world:
+        raise ValueError("the layout was planned for another number of ranks")
+    backend.bind(layout, ex.rank)
+    return _invert([data], freq, layout, [backend], ex, clock, sparse)
+
+
+def invert_strips_local(datas: Sequence[StripData], freq, layout: StripLayout, backend: StripBackend,
                         stages: Optional[list] = None, sparse: bool = True):
     """All ranks' stages in ONE process on one device, the exchanges done in
     memory (the single-GPU check of the decomposition and its kernels, and the
-    per-rank cost breakdown of the N-GPU split). Rank r's stages run on its
-    own strip + halo buffer (`backend.spawn()` per rank, kept as
-    `backend.ranks`), in the distributed order: every rank grids its strip,
-    the halos move to the next rank, pass A runs per strip, the pass-A blocks
-    are regrouped per image-row strip (the all-to-all) and pass B runs per
-    image-row strip. `sparse`: the regrouping moves only each rank's live
-    rows (as the distributed sparse all-to-all). `stages` (a list,
+    per-rank cost breakdown of the N-GPU split): the distributed invert's own
+    driver over every rank. Rank r's stages run on its own strip + halo buffer
+    (`backend.spawn()` per rank, kept as `backend.ranks`). `stages` (a list,
     diagnostic): filled with one dict per rank of synchronised seconds (grid,
-    halo, rows, pack, assemble, cols) and the bytes the rank would send in
-    the all-to-all (a2a_send_bytes). Returns the normalised dirty image
-    (npix_x, npix_y)."""
-    import time  # pylint: disable=import-outside-toplevel
-
-    world = layout.world
+    halo, rows, pack, assemble, cols, final) and the bytes the rank would send
+    to the others in the all-to-all (a2a_send_bytes). Returns the normalised
+    dirty image (npix_x, npix_y)."""
+    world, backend = layout.world, _adopt(backend)
     if len(datas) != world:
         raise ValueError("one StripData per strip")
     if stages is not None:
         stages[:] = [{} for _ in range(world)]
-    dev = getattr(backend, "device", None)
-    on_gpu = dev is not None and torch.device(dev).type == "cuda"
+    if not backend.ranks or len(backend.ranks) != world:
+        backend.ranks = [backend] + [_adopt(backend.spawn()) for _ in range(world - 1)]
+    for r in range(world):
+        backend.ranks[r].bind(layout, r)
+    ex = _LocalExchange(layout)
+    clock = _Clock(stages, backend.device, False, ex.stage_names)
+    return _invert(datas, freq, layout, backend.ranks, ex, clock, sparse)
 
-    def timed(r, name, fn):
-        if stages is None:
-            return fn()
-        if on_gpu:
-            torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        out = fn()
-        if on_gpu:
-            torch.cuda.synchronize(dev)
-        stages[r][name] = stages[r].get(name, 0.0) + time.perf_counter() - t0
-        return out
-
-    ranks = getattr(backend, "ranks", None)
-    if not ranks or len(ranks) != world:
-        ranks = [backend] + [backend.spawn() for _ in range(world - 1)]
-        backend.ranks = ranks
-    for r in range(world):
-        ranks[r].bind(layout, r)
-    bufs, sums = [None] * world, [None] * world
-    for r in range(world):
-        bufs[r], sums[r] = timed(r, "grid", lambda r=r: ranks[r].grid_strip(datas[r], freq))
-    sumw = sums[0].clone()
-    for sw in sums[1:]:
-        sumw = sumw + sw
-    hs = [layout.rows(r)[1] - layout.rows(r)[0] for r in range(world)]
-    nplanes = int(getattr(backend, "nplanes", 1))
-    rowsel = (lambda b, lo, hi: b[lo:hi]) if nplanes == 1 else (lambda b, lo, hi: b[:, lo:hi])
-    if world > 1:
-        halos = []
-        for r in range(world):
-            halos.append(rowsel(bufs[r], hs[r], hs[r] + layout.halo).clone())
-            rowsel(bufs[r], hs[r], hs[r] + layout.halo).zero_()
-        for r in range(world):
-            timed(r, "halo", lambda r=r: rowsel(bufs[r], 0, layout.halo).add_(halos[(r - 1) % world]))
-    if nplanes > 1:
-        # per w plane: every rank's pass A, the regrouping, every rank's pass B
-        # with the plane's w screen into its image rows; then the corrections
-        accs = []
-        for s in range(world):
-            i0, i1 = layout.image_rows(s)
-            accs.append(torch.empty((i1 - i0, backend.npix_y), dtype=torch.float64, device=bufs[0].device))
-        for p in range(nplanes):
-            Hs, lives, sends = _local_pass_a(ranks, [b[p] for b in bufs], hs, p, sparse, on_gpu, timed, backend,
-                                             layout, stages)
-            for s in range(world):
-                i0, i1 = layout.image_rows(s)
-                b0, b1 = i0 // COL_BLOCK, i1 // COL_BLOCK
-                if world == 1:
-                    Hm = Hs[0]
-                elif sends is not None:
-                    recv = torch.cat([snd[b0:b1].reshape(-1) for snd in sends[0]])
-                    Hm = timed(s, "assemble", lambda b0=b0, b1=b1, recv=recv: _unpack_rows(
-                        recv, b1 - b0, layout, sends[1], recv.dtype, sends[3]).to(torch.float64))
-                else:
-                    def regroup(b0=b0, b1=b1):
-                        pieces, idx = _local_pieces(Hs, b0, b1, backend, lives)
-                        return _assemble_H(pieces, b1 - b0, layout, Hs[0].device, _wire(Hs[0][:0], backend).dtype,
-                                           idx).to(torch.float64)
-                    Hm = timed(s, "assemble", regroup)
-                timed(s, "cols", lambda s=s, Hm=Hm, i0=i0, i1=i1: ranks[s].pass_cols_wplane(
-                    Hm.contiguous(), i0, i1, p, p == 0, accs[s]))
-        out = []
-        for s in range(world):
-            ranks[s].mark_clean()
-            i0, i1 = layout.image_rows(s)
-            out.append(timed(s, "final", lambda s=s, i0=i0, i1=i1: ranks[s].finish_rows(accs[s], i0, i1, norm=sumw)))
-        return torch.cat(out, dim=0)
-    Hs, lives, sends = _local_pass_a(ranks, bufs, hs, 0, sparse, on_gpu, timed, backend, layout, stages)
-    for r in range(world):
-        ranks[r].mark_clean()
-    out = []
-    for s in range(world):
-        i0, i1 = layout.image_rows(s)
-        b0, b1 = i0 // COL_BLOCK, i1 // COL_BLOCK
-        if world == 1:
-            Hm = Hs[0]
-        elif sends is not None:
-            recv = torch.cat([snd[b0:b1].reshape(-1) for snd in sends[0]])
-            Hm = timed(s, "assemble", lambda b0=b0, b1=b1, recv=recv: _unpack_rows(
-                recv, b1 - b0, layout, sends[1], recv.dtype, sends[3]).to(torch.float64))
-        else:
-            def regroup(b0=b0, b1=b1):
-                pieces, idx = _local_pieces(Hs, b0, b1, backend, lives)
-                return _assemble_H(pieces, b1 - b0, layout, Hs[0].device, _wire(Hs[0][:0], backend).dtype,
-                                   idx).to(torch.float64)
-            Hm = timed(s, "assemble", regroup)
-        out.append(timed(s, "cols", lambda s=s, Hm=Hm, i0=i0, i1=i1: ranks[s].pass_cols(Hm.contiguous(), i0, i1,
-                                                                                         norm=sumw)))
-    return torch.cat(out, dim=0)

@@ -19,7 +19,7 @@ from ska_sdp_cip_amd import strips
 from ska_sdp_cip_amd.strips import COL_BLOCK
 
 
-class NumpyStripBackend:
+class NumpyStripBackend(strips.StripBackend):
     def __init__(self, prm: dict, px: float, py: float, npix_x: int, npix_y: int, rows=None):
         self.prm, self.px, self.py = prm, float(px), float(py)
         self.npix_x, self.npix_y = int(npix_x), int(npix_y)

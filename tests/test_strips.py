@@ -4,8 +4,9 @@ the strip plan covers every visibility exactly once, the single-process
 emulation of the halo exchange / all-to-all equals the one-shot image, and a
 world-size-2 (and 3) gloo run of the real collectives gives the single-process
 image at 1e-13 - with the CPU restatement of the per-rank stages
-(tests/_strip_np.py) standing in for the GPU. The GPU form of the same checks
-is in test_gpu_strips.py.
+(tests/_strip_np.py) standing in for the GPU; a recorder in the gloo ranks pins
+the per-rank order of backend stages and collectives. The GPU form of the same
+checks is in test_gpu_strips.py.
 """
 import os
 import socket
@@ -128,6 +129,30 @@ def test_strip_emulation_equals_one_shot(world, W):
         assert sum(b.rows[1] for b in be.ranks) == prm["nv"] + world * (W - 1)
 
 
+def test_backend_without_the_base_class_still_works():
+    # a backend written before StripBackend existed: the stages and nothing
+    # else (no base class, no ranks / device / single / live_rows); the drivers
+    # give it the base's defaults
+    from _strip_np import NumpyStripBackend
+
+    members = {k: v for k, v in vars(NumpyStripBackend).items() if k == "__init__" or not k.startswith("__")}
+    members["spawn"] = lambda self: Plain(self.prm, self.px, self.py, self.npix_x, self.npix_y, rows=self.rows)
+    Plain = type("Plain", (), members)
+    world, W = 3, 6
+    uvw, f, vis, w, px = _case()
+    prm = _prm(px, W)
+    layout = strips.plan_strips(torch.from_numpy(uvw), torch.from_numpy(f), _P(prm), px, NPIX, NPIX, world)
+    datas = _strip_datas(uvw, f, vis, w, px, prm, layout)
+    be = Plain(prm, px, px, NPIX, NPIX)
+    assert not isinstance(be, strips.StripBackend) and not hasattr(be, "ranks")
+    img = strips.invert_strips_local(datas, torch.from_numpy(f), layout, be).numpy()
+    full = oracle.ms2dirty(uvw, f, vis, w, NPIX, NPIX, px, px, support=W, nthreads=1) / w.astype(np.float64).sum()
+    assert np.abs(img - full).max() < 1e-13 * max(1.0, np.abs(full).max())
+    assert len(be.ranks) == world and be.ranks[0] is be and all(isinstance(b, Plain) for b in be.ranks)
+    for b in be.ranks:
+        assert float(b.grid.abs().max()) == 0.0 and not b.dirty
+
+
 @pytest.mark.parametrize("world,W", [(1, 6), (2, 6), (3, 4), (5, 8)])
 def test_wstacking_strip_emulation_equals_one_shot(world, W):
     # the reference's own gridding mode split by uv strips: every plane's
@@ -150,7 +175,9 @@ def test_wstacking_strip_emulation_equals_one_shot(world, W):
         assert float(b.grid.abs().max()) == 0.0 and not b.dirty
 
 
-def _worker(rank, world, port, q, W, wstack=False):
+def _join_gloo(rank, world, port, W, wstack):
+    """A spawned rank's start: the import paths, the gloo group, the case and
+    this rank's strip -> (NumpyStripBackend, uvw, f, vis, w, px, prm, layout, data)."""
     import sys
     from pathlib import Path
 
@@ -169,7 +196,12 @@ def _worker(rank, world, port, q, W, wstack=False):
         prm = _prm(px, W)
     layout = strips.plan_strips(torch.from_numpy(uvw), torch.from_numpy(f), _P(prm), px, NPIX, NPIX, world)
     data = _strip_datas(uvw, f, vis, w, px, prm, layout)[rank]  # each rank holds only its strip
-    be = NumpyStripBackend(prm, px, px, NPIX, NPIX)
+    return NumpyStripBackend, uvw, f, vis, w, px, prm, layout, data
+
+
+def _worker(rank, world, port, q, W, wstack=False):
+    backend, uvw, f, vis, w, px, prm, layout, data = _join_gloo(rank, world, port, W, wstack)
+    be = backend(prm, px, px, NPIX, NPIX)
     img = strips.invert_strips(data, torch.from_numpy(f), layout, be, dst=0)
     # two more inverts with the gather in flight while the next one grids
     p1 = strips.invert_strips(data, torch.from_numpy(f), layout, be, dst=0, gather_async=True)
@@ -200,6 +232,93 @@ def test_strip_halo_exchange_gloo(world, W, wstack):
     err, peak, left = q.get(timeout=5)
     assert err < 1e-13 * max(1.0, peak)
     assert left == 0.0
+
+
+STAGE_CALLS = ("grid_strip", "mark_clean", "pass_rows", "pass_rows_packed", "pass_cols", "pass_cols_wplane",
+               "finish_rows")
+DIST_CALLS = ("batch_isend_irecv", "all_reduce", "all_gather", "all_to_all_single", "gather")
+
+
+def _record(obj, names, log, depth):
+    """Replace obj's callables `names` by ones that append their name to `log`;
+    only the outermost call is logged (a recorded call made from inside another -
+    the base pass_rows_packed's pass_rows - is part of that stage)."""
+    def wrapped(name, fn):
+        def call(*args, **kwargs):
+            if depth[0] == 0:
+                log.append(name)
+            depth[0] += 1
+            try:
+                return fn(*args, **kwargs)
+            finally:
+                depth[0] -= 1
+        return call
+
+    for name in names:
+        setattr(obj, name, wrapped(name, getattr(obj, name)))
+
+
+def _order_worker(rank, world, port, q, W, sparse, knows_live, wstack):
+    base, uvw, f, vis, w, px, prm, layout, data = _join_gloo(rank, world, port, W, wstack)
+
+    class KnowsLiveRows(base):
+        """Knows its live rows before pass A: the rows of its buffer plane that hold a non-zero."""
+
+        def live_rows(self, h, plane=0):
+            buf = self.grid if self.nplanes == 1 else self.grid[plane]
+            return (buf[:h] != 0).reshape(h, -1).any(dim=1)
+
+    be = (KnowsLiveRows if knows_live else base)(prm, px, px, NPIX, NPIX)
+    log, depth = [], [0]
+    _record(be, STAGE_CALLS, log, depth)
+    _record(dist, DIST_CALLS, log, depth)
+    img = strips.invert_strips(data, torch.from_numpy(f), layout, be, dst=0, sparse=sparse)
+    if rank == 0:
+        full = oracle.ms2dirty(uvw, f, vis, w, NPIX, NPIX, px, px, support=W, do_wstacking=wstack,
+                               nthreads=1) / w.astype(np.float64).sum()
+        q.put((log, int(prm["nplanes"]) if wstack else 1, float(np.abs(img.numpy() - full).max()),
+               float(np.abs(full).max())))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("case", ["sparse", "dense", "knows_live", "knows_live_wstack"])
+def test_per_rank_call_order_gloo(case):
+    """The per-rank sequence of backend stages and collectives of the
+    distributed invert (rank 0 of 2, W = 6): the N-GPU speed depends on it (a
+    collective more, or pass A on the wrong side of the mask all-gather, costs
+    a rendezvous per plane). `bind` comes first in every case and is not
+    recorded; with w-stacking `mark_clean` may come anywhere after the last
+    plane's pass A."""
+    world, W = 2, 6
+    sparse, knows_live, wstack = case != "dense", case.startswith("knows_live"), case.endswith("wstack")
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_order_worker, args=(r, world, port, q, W, sparse, knows_live, wstack))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=240)
+    assert all(p.exitcode == 0 for p in procs)
+    log, nplanes, err, peak = q.get(timeout=5)
+    head = ["grid_strip", "batch_isend_irecv", "all_reduce"]
+    if wstack:
+        assert nplanes > W
+        want = head + ["all_gather", "pass_rows_packed", "all_to_all_single", "pass_cols_wplane"] * nplanes + \
+            ["finish_rows", "gather"]
+        at = log.index("mark_clean")
+        assert "pass_rows_packed" not in log[at:]
+        log = log[:at] + log[at + 1:]
+    elif knows_live:
+        want = head + ["all_gather", "pass_rows_packed", "mark_clean", "all_to_all_single", "pass_cols", "gather"]
+    else:
+        want = head + ["pass_rows", "mark_clean"] + ["all_gather"] * sparse + ["all_to_all_single", "pass_cols",
+                                                                               "gather"]
+    assert log == want
+    if knows_live:
+        assert err < 1e-13 * max(1.0, peak)
 
 
 def test_strips_with_empty_strips_and_no_data():

@@ -244,7 +244,7 @@ def wstrips_model(args):
     stage_max = {k: max(p.get(k, 0.0) for p in pr) for k in ("grid", "rows", "pack", "assemble", "cols", "final")}
     t1 = sum(out[1]["per_rank_ms"][0].get(k, 0.0) for k in ("grid", "rows", "cols", "final"))
     nplanes, W, nu = int(params.nplanes), int(params.support), int(params.nu)
-    # one plane's pass-A output as it crosses the all-to-all (complex64 for the packed class, strips._wire)
+    # one plane's pass-A output as it crosses the all-to-all (complex64 for the packed class, StripBackend.wire)
     H_bytes = [(npix // 4) * (b - a) * 4 * (8 if args.single else 16) for a, b in out[N]["strip_rows"]]
     # the sparse all-to-all's bytes per rank, summed over the planes (measured)
     send_bytes = [int(p.get("a2a_send_bytes", 0.0) * 1e-3) for p in out[N]["per_rank_ms"]]
