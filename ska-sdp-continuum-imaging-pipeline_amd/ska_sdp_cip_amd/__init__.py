@@ -12,7 +12,9 @@ clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_imaging_weights`), multi-term multi-frequency synthesis (`mfs.py`,
 `cip_mfs_clean`), multiscale CLEAN (`multiscale.py`, `cip_ms_convolve`,
 `cip_ms_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`), the sky-model
-predict (`skymodel.py`, `cip_dft_predict`) and the `uvw_tiling` package.
+predict (`skymodel.py`, `cip_dft_predict`), the image noise and the island
+mask behind the major cycles' `auto_threshold` and `auto_mask` (`noise.py`,
+`cip_image_noise`, `cip_auto_mask`) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -26,6 +28,15 @@ from .invert import (  # noqa: E402
     invert_measurement_set,
 )
 from .predict import device_residual, ducc_predict  # noqa: E402
+from . import noise  # noqa: E402
+from .noise import (  # noqa: E402
+    MAD_TO_SIGMA,
+    auto_mask,
+    device_auto_mask,
+    device_image_noise,
+    device_image_select,
+    image_noise,
+)
 from .deconvolve import device_hogbom_clean, device_major_cycles, hogbom_clean  # noqa: E402
 # `restore.restore` (numpy in -> numpy out) stays in its module: exported here
 # it would hide the module of the same name
@@ -145,4 +156,11 @@ __all__ = [
     "SkyModel",
     "device_dft_predict",
     "dft_predict",
+    "noise",
+    "MAD_TO_SIGMA",
+    "device_image_select",
+    "device_image_noise",
+    "device_auto_mask",
+    "image_noise",
+    "auto_mask",
 ]

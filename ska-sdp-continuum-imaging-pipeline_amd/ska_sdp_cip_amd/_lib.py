@@ -1,6 +1,7 @@
 """
 ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h,
-include/cip_mfs.h, include/cip_cal.h, include/cip_dft.h and include/cip_ms.h).
+include/cip_mfs.h, include/cip_cal.h, include/cip_dft.h, include/cip_ms.h and
+include/cip_noise.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -337,6 +338,42 @@ MS_PROTOTYPES = {
 }
 
 
+class NoiseResult(ctypes.Structure):
+    """Mirror of `cip_noise_result` (include/cip_noise.h)."""
+
+    _fields_ = [
+        ("count", ctypes.c_int64),
+        ("median", ctypes.c_double),
+        ("mad", ctypes.c_double),
+        ("sigma", ctypes.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class MaskResult(ctypes.Structure):
+    """Mirror of `cip_mask_result` (include/cip_noise.h)."""
+
+    _fields_ = [(name, ctypes.c_int64) for name in ("n_seed", "n_island", "n_out", "rounds")]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# And for include/cip_noise.h, the seventh (the results and the two scalars of the select are HOST memory).
+MAD_TO_SIGMA = 1.482602218505602  # CIP_MAD_TO_SIGMA
+MASK_POSITIVE = 1  # CIP_MASK_POSITIVE
+MASK_CONN4 = 2  # CIP_MASK_CONN4
+NOISE_PROTOTYPES = {
+    "cip_image_select": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _pi64, _pf64]),
+    "cip_image_noise": (_i32, [_vp, _i64, _i64, _vp, _vp, ctypes.POINTER(NoiseResult)]),
+    "cip_auto_mask": (_i32, [_vp, _i64, _i64, _f64, _f64, _vp, _vp, _i32, _vp, _vp, ctypes.POINTER(MaskResult)]),
+}
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
     global _LIB  # pylint: disable=global-statement
@@ -351,7 +388,8 @@ def lib() -> ctypes.CDLL:
         )
     so = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items(),
-                                      *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items(), *MS_PROTOTYPES.items()):
+                                      *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items(), *MS_PROTOTYPES.items(),
+                                      *NOISE_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

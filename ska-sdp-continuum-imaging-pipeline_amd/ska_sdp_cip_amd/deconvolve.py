@@ -12,6 +12,7 @@ is subtracted, so a run is bit-identical to that numpy statement.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import numpy as np
@@ -20,6 +21,7 @@ from . import _lib
 from ._call import STREAM, call, check_array, require_gpu, target_device, to_device
 from .gridder import device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
+from .noise import device_auto_mask, device_image_noise
 from .predict import device_residual
 from .restore import device_fit_beam, device_restore
 from .weighting import device_imaging_weights
@@ -137,27 +139,82 @@ def _host_clean(device_clean, residual, psf, *hinv, mask, model, return_componen
     return model_d, res_d, info
 
 
-def _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, restore):
-    """The cycle loop of `device_major_cycles` and `mfs.device_mfs_major_cycles`.
-    `clean(threshold, probe)` returns the minor cycle's info (`probe`: niter=0,
-    the peak under the mask with nothing changed), `reinvert()` replaces the
-    residual by the re-inverted one, `restore(result)` (or None) adds the
-    restored images. Adds `peaks`, `components` and `stop_reason` to `result`."""
-    peaks, components = [], []
+def _auto_options(auto_threshold, auto_mask):
+    """The two noise options as `_major_cycles` takes them: `auto_threshold` as a
+    float, `auto_mask` as (seed_sigmas, grow_sigmas), a single number meaning
+    both; None stays None. The drivers call this before any device work, so a
+    bad option raises ValueError without an invert."""
+    if auto_threshold is not None:
+        auto_threshold = float(auto_threshold)
+        if not auto_threshold >= 0.0:
+            raise ValueError(f"auto_threshold must be >= 0 and not NaN, got {auto_threshold}")
+    if auto_mask is not None:
+        pair = tuple(auto_mask) if isinstance(auto_mask, (tuple, list)) else (auto_mask, auto_mask)
+        if len(pair) != 2:
+            raise ValueError(f"auto_mask must be (seed_sigmas, grow_sigmas) or one number, got {auto_mask!r}")
+        seed, grow = float(pair[0]), float(pair[1])
+        if not (math.isfinite(seed) and seed >= grow > 0.0):
+            raise ValueError(f"auto_mask needs finite seed_sigmas >= grow_sigmas > 0, got {auto_mask!r}")
+        auto_mask = (seed, grow)
+    return auto_threshold, auto_mask
+
+
+def _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, restore, *, mask=None,
+                  noise_image=None, auto_threshold=None, auto_mask=None):
+    """The cycle loop of `device_major_cycles`, `mfs.device_mfs_major_cycles`
+    and `multiscale.device_ms_major_cycles`. `clean(threshold, probe, mask)`
+    returns the minor cycle's info (`probe`: niter=0, the peak under the mask
+    with nothing changed), `reinvert()` replaces the residual by the
+    re-inverted one, `restore(result)` (or None) adds the restored images. Adds
+    `peaks`, `components` and `stop_reason` to `result`.
+
+    With `auto_threshold` or `auto_mask` every cycle starts from the noise
+    sigma_c of `noise_image()` (`noise.device_image_noise`): a sigma_c that is
+    not finite and > 0 ends the loop ("noise"); `auto_mask` = (seed, grow) grows
+    the mask A (zeros at first) by the islands of `noise_image()` above seed
+    sigma_c that extend down to grow sigma_c inside `mask`, and A stands in for
+    `mask`; max(threshold, auto_threshold sigma_c) stands in for `threshold`.
+    `result` then gains `noise` (sigma_c of every cycle begun) and, with
+    `auto_mask`, `auto_mask` (the final A). Both options come through
+    `_auto_options`."""
+    peaks, components, sigmas = [], [], []
     stop_reason = "n_major"
+    measure = auto_threshold is not None or auto_mask is not None
+    grown = None
+    if auto_mask is not None:
+        seed_sigmas, grow_sigmas = auto_mask
+        image = noise_image()
+        grown = torch.zeros(tuple(image.shape), dtype=torch.uint8, device=image.device)
     for _cycle in range(int(n_major)):
-        start = clean(threshold, True)
+        cycle_mask, cycle_floor = mask, threshold
+        if measure:
+            image = noise_image()
+            sigma = device_image_noise(image)["sigma"]
+            sigmas.append(sigma)
+            if not (math.isfinite(sigma) and sigma > 0.0):
+                stop_reason = "noise"
+                break
+            if grown is not None:
+                device_auto_mask(image, seed_sigmas * sigma, grow_sigmas * sigma, region=mask, base=grown, out=grown)
+                cycle_mask = grown
+            if auto_threshold is not None:
+                cycle_floor = max(threshold, auto_threshold * sigma)
+        start = clean(cycle_floor, True, cycle_mask)
         if start["stop_reason"] == _lib.CIP_CLEAN_EMPTY:
             stop_reason = "empty"
             break
         peak = abs(start["peak"])
-        if peak <= threshold:
+        if peak <= cycle_floor:
             stop_reason = "threshold"
             break
         peaks.append(peak)
-        components.append(clean(max(threshold, cycle_fraction * peak), False)["niter_done"])
+        components.append(clean(max(cycle_floor, cycle_fraction * peak), False, cycle_mask)["niter_done"])
         reinvert()
     result.update(peaks=peaks, components=components, stop_reason=stop_reason)
+    if measure:
+        result["noise"] = sigmas
+    if grown is not None:
+        result["auto_mask"] = grown
     if restore is not None:
         restore(result)
     return result
@@ -244,6 +301,8 @@ def device_major_cycles(
     robust: float = 0.0,
     restore: bool = False,
     beam: Optional[dict] = None,
+    auto_threshold: Optional[float] = None,
+    auto_mask: Optional[tuple] = None,
 ):
     """
     Major cycles on device-resident data (an `npix` x `npix` image with pixels
@@ -272,8 +331,23 @@ def device_major_cycles(
     `restore=True` adds `beam` (the clean beam, `restore.device_fit_beam` of
     the loop's PSF unless `beam` is passed) and `restored` (the final model
     convolved with it plus the final residual, `restore.device_restore`).
+
+    `auto_threshold` (a number of sigmas) and `auto_mask` ((seed_sigmas,
+    grow_sigmas), or one number for both) drive the loop by the noise of the
+    residual image, measured on the device at the start of every cycle
+    (`noise.device_image_noise`; sigma_c = 1.4826 MAD): the cycle's threshold
+    is max(threshold, auto_threshold sigma_c) wherever `threshold` stands
+    above, and components go only into the mask A, which starts empty and
+    every cycle gains the islands of the residual above seed_sigmas sigma_c
+    that extend down to grow_sigmas sigma_c (`noise.device_auto_mask`, inside
+    `mask` when one is given). A sigma_c that is not finite and > 0 ends the
+    loop with `stop_reason` "noise". The result then also holds `noise` (the
+    sigma_c of every cycle begun, the stopping one included) and, with
+    `auto_mask`, `auto_mask` (the final A). With both None (the default)
+    nothing is measured and neither key exists.
     """
     require_gpu()
+    auto_threshold, auto_mask = _auto_options(auto_threshold, auto_mask)
     npix = int(npix)
     kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
     wgt, _ = device_imaging_weights(uvw, freq, wgt, npix, npix, pixsize, pixsize, weighting=weighting, robust=robust)
@@ -282,9 +356,9 @@ def device_major_cycles(
                                   reuse_plan=True, **kw)
     model = torch.zeros((npix, npix), dtype=torch.float64, device=uvw.device)
 
-    def clean(cycle_threshold, probe):
+    def clean(cycle_threshold, probe, cycle_mask):
         return device_hogbom_clean(residual, psf, gain=gain, threshold=cycle_threshold, niter=0 if probe else niter,
-                                   mask=mask, model=None if probe else model, inplace=True)[2]
+                                   mask=cycle_mask, model=None if probe else model, inplace=True)[2]
 
     def reinvert():
         vis_res = device_residual(uvw, freq, vis, model, pixsize, None, reuse_plan=True, **kw)
@@ -296,4 +370,5 @@ def device_major_cycles(
         result["restored"] = device_restore(model, residual, result["beam"])
 
     return _major_cycles({"model": model, "residual": residual, "psf": psf}, n_major, threshold, cycle_fraction,
-                         clean, reinvert, add_restored if restore else None)
+                         clean, reinvert, add_restored if restore else None, mask=mask,
+                         noise_image=lambda: residual, auto_threshold=auto_threshold, auto_mask=auto_mask)

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._call import check_array, check_rows, require_gpu
-from .deconvolve import _device_clean, _host_clean, _major_cycles
+from .deconvolve import _auto_options, _device_clean, _host_clean, _major_cycles
 from .gridder import device_dirty2ms, device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .restore import device_fit_beam, device_restore
@@ -285,6 +285,8 @@ def device_mfs_major_cycles(
     restore: bool = False,
     beam: Optional[dict] = None,
     alpha_cut: float = 0.0,
+    auto_threshold: Optional[float] = None,
+    auto_mask: Optional[tuple] = None,
 ):
     """
     Wide-band major cycles on device-resident data: the structure of
@@ -307,8 +309,12 @@ def device_mfs_major_cycles(
     `device_restore(models[t], sum_q hinv[t][q] residuals[q], beam)`, and, for
     nterms >= 2, `alpha` = restored[1] / restored[0] where |restored[0]| >
     `alpha_cut`, NaN elsewhere.
+
+    `auto_threshold` and `auto_mask` as for `device_major_cycles`; the noise
+    and the islands are those of the term-0 residual, residuals[0].
     """
     require_gpu()
+    auto_threshold, auto_mask = _auto_options(auto_threshold, auto_mask)
     nterms, npix = _check_nterms(nterms), int(npix)
     ref = _mid_band(freq) if ref_freq is None else float(ref_freq)
     kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
@@ -322,9 +328,9 @@ def device_mfs_major_cycles(
     models = torch.zeros_like(residuals)
     degrid = scratch if scratch.dtype == torch.complex128 else None
 
-    def clean(cycle_threshold, probe):
+    def clean(cycle_threshold, probe, cycle_mask):
         return device_mfs_clean(residuals, psfs, hinv, gain=gain, threshold=cycle_threshold,
-                                niter=0 if probe else niter, mask=mask, model=None if probe else models,
+                                niter=0 if probe else niter, mask=cycle_mask, model=None if probe else models,
                                 inplace=True)[2]
 
     def reinvert():
@@ -344,4 +350,6 @@ def device_mfs_major_cycles(
 
     result = {"models": models, "residuals": residuals, "psfs": psfs, "hessian": hessian, "hinv": hinv,
               "ref_freq": ref}
-    return _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, add_restored if restore else None)
+    return _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, add_restored if restore else None,
+                         mask=mask, noise_image=lambda: residuals[0], auto_threshold=auto_threshold,
+                         auto_mask=auto_mask)

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._call import STREAM, call, check_array, require_gpu
-from .deconvolve import _device_clean, _host_clean, _major_cycles
+from .deconvolve import _auto_options, _device_clean, _host_clean, _major_cycles
 from .gridder import device_ms2dirty
 from .invert import DO_WSTACKING, EPSILON
 from .predict import device_residual
@@ -267,6 +267,8 @@ def device_ms_major_cycles(
     robust: float = 0.0,
     restore: bool = False,
     beam: Optional[dict] = None,
+    auto_threshold: Optional[float] = None,
+    auto_mask: Optional[tuple] = None,
 ):
     """
     Multiscale major cycles on device-resident data: the structure of
@@ -288,8 +290,13 @@ def device_ms_major_cycles(
     `restore=True` adds `beam` (`restore.device_fit_beam` of the PSF unless
     `beam` is passed) and `restored` (`device_restore` of the summed model and
     the final residual).
+
+    `auto_threshold` and `auto_mask` as for `device_major_cycles`; the noise
+    and the islands are those of the unsmoothed residual image, and the one
+    mask holds for every scale.
     """
     require_gpu()
+    auto_threshold, auto_mask = _auto_options(auto_threshold, auto_mask)
     widths, npix = _check_widths(widths), int(npix)
     nscales = len(widths)
     kw = dict(epsilon=epsilon, support=support, do_wstacking=do_wstacking)
@@ -307,13 +314,13 @@ def device_ms_major_cycles(
     residuals = torch.empty_like(models)
     smoothed = False  # whether `residuals` holds the scales of the current `residual`
 
-    def clean(cycle_threshold, probe):
+    def clean(cycle_threshold, probe, cycle_mask):
         nonlocal smoothed
         if not smoothed:  # once per cycle: the probe changes nothing, so the CLEAN after it starts from the same stack
             device_scale_residuals(residual, widths, out=residuals)
             smoothed = True
         return device_ms_clean(residuals, cross_psfs, select_weight, flux_scale, gain=gain, threshold=cycle_threshold,
-                               niter=0 if probe else niter, mask=mask, model=None if probe else models,
+                               niter=0 if probe else niter, mask=cycle_mask, model=None if probe else models,
                                inplace=True)[2]
 
     def reinvert():
@@ -330,4 +337,5 @@ def device_ms_major_cycles(
 
     result = {"model": model, "models": models, "residual": residual, "psf": psf, "cross_psfs": cross_psfs,
               "select_weight": select_weight, "flux_scale": flux_scale, "widths": widths}
-    return _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, add_restored if restore else None)
+    return _major_cycles(result, n_major, threshold, cycle_fraction, clean, reinvert, add_restored if restore else None,
+                         mask=mask, noise_image=lambda: residual, auto_threshold=auto_threshold, auto_mask=auto_mask)

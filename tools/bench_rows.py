@@ -71,6 +71,19 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     sum in fp64 on the same device in the same run (64
                     components: best of --repeat; 1024: one run); also written
                     to profiles/dft_predict_c3.json
+  --mode noise      device_image_noise and device_auto_mask (noise.py) on the
+                    scene of --mode clean at --noise-npix^2 (8192) with seeded
+                    Gaussian pixel noise: ms per call, interleaved in the same
+                    run with what torch offers for the same numbers
+                    (kthvalue of the flattened image, then of |x - median|),
+                    both lists of times and their spread; the full reads of
+                    the image the two selects make (replayed in numpy from the
+                    digit widths and the compaction capacity), the GB/s that
+                    implies beside a device copy of the same image; the mask
+                    at (5 sigma, 3 sigma) and its rounds; and one major
+                    cycle's predict + re-invert on bench.py's C3 inputs, with
+                    the noise and the mask at C3's image size beside it; also
+                    written to profiles/noise_c3.json
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -861,11 +874,166 @@ def restore(args):
     path.write_text(json.dumps(result, indent=1) + "\n")
     return result
 
+SELECT_DIGITS = (12, 13, 13, 13, 13)  # kSelBits of csrc/cip_noise.hip
+SELECT_COMPACT_CAP = 1 << 16  # kCompactCap
+
+
+def _select_replay(values, rank):
+    """The radix select of csrc/cip_noise.hip replayed in numpy on the finite
+    `values`: (the value of `rank`, the full reads of the image it makes)."""
+    bits = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+    top = np.uint64(1) << np.uint64(63)
+    keys = np.where(bits >> np.uint64(63) != 0, ~bits, bits | top)
+    shift, prefix, reads, compacted = 64, 0, 0, False
+    for k, width in enumerate(SELECT_DIGITS):
+        shift -= width
+        digit = ((keys >> np.uint64(shift)) & np.uint64((1 << width) - 1)).astype(np.int64)
+        hist = np.bincount(digit, minlength=1 << width)
+        reads += 0 if compacted else 1
+        b = int(np.searchsorted(np.cumsum(hist), rank, side="right"))
+        rank -= int(hist[:b].sum())
+        prefix |= b << shift
+        keys = keys[digit == b]
+        if not compacted and k + 1 < len(SELECT_DIGITS) and keys.size <= SELECT_COMPACT_CAP:
+            compacted, reads = True, reads + 1  # the compaction reads the image once more
+    key = np.uint64(prefix)
+    out = np.array([key & ~top if key >> np.uint64(63) else ~key], dtype=np.uint64)
+    return float(out.view(np.float64)[0]), reads
+
+
+def noise_rows(args):
+    """ms per device_image_noise / device_auto_mask call beside torch.kthvalue, a copy and a C3 major cycle."""
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench  # the flagship workload's own inputs
+
+    from ska_sdp_cip_amd import _lib, gridder, noise, predict, synthetic as syn
+
+    dev = torch.device("cuda", 0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def scene(npix):
+        """The image of --mode clean (lognormal point sources convolved with a PSF patch) plus Gaussian noise."""
+        pn = min(args.patch, npix)
+        uvw_h = syn.uvw_tracks(args.rows, 64, array_radius_m=4000.0)
+        freq_h = syn.channel_frequencies(args.nchan)
+        px = syn.pixel_size_for_grid(uvw_h, freq_h, npix, support=8)
+        psf_full, _ = gridder.device_ms2dirty(torch.from_numpy(uvw_h).to(dev), torch.from_numpy(freq_h).to(dev), None,
+                                              None, npix, npix, px, px, support=8, psf=True, normalise=True)
+        o, c = npix // 2 - pn // 2, pn // 2
+        psf = psf_full[o:o + pn, o:o + pn].contiguous()
+        del psf_full
+        _lib.lib().cip_release_workspace()  # the invert's grid is not needed any more
+        rng = np.random.default_rng(20241019)
+        g = torch.Generator(device=dev)
+        g.manual_seed(20241021)
+        image = torch.randn((npix, npix), dtype=torch.float64, device=dev, generator=g) * args.noise_sigma
+        for i, j, flux in zip(rng.integers(0, npix, args.sources), rng.integers(0, npix, args.sources),
+                              rng.lognormal(0.0, 1.0, args.sources)):
+            i, j = int(i), int(j)
+            i0, i1, j0, j1 = max(0, i - c), min(npix, i - c + pn), max(0, j - c), min(npix, j - c + pn)
+            image[i0:i1, j0:j1] += float(flux) * psf[i0 - i + c:i1 - i + c, j0 - j + c:j1 - j + c]
+        return image
+
+    def torch_noise(image):
+        flat = image.view(-1)
+        k = (flat.numel() - 1) // 2 + 1  # kthvalue counts from 1
+        median = torch.kthvalue(flat, k).values
+        mad = torch.kthvalue((flat - median).abs(), k).values
+        return float(median), float(mad)
+
+    def noise_and_mask(image):
+        got = noise.device_image_noise(image)
+        return got, noise.device_auto_mask(image, 5.0 * got["sigma"], 3.0 * got["sigma"])[1]
+
+    n = args.noise_npix
+    image = scene(n)
+    noise.device_image_noise(image)  # warm-up: workspace, kernels
+    torch_noise(image)
+    hip_ms, torch_ms = [], []
+    for _ in range(args.repeat):  # interleaved: both see the same machine
+        t, got = timed(lambda: noise.device_image_noise(image))
+        hip_ms.append(round(t, 3))
+        t, ref = timed(lambda: torch_noise(image))
+        torch_ms.append(round(t, 3))
+    # the same call with a region of ones: what the byte per pixel of the region costs
+    ones = torch.ones((n, n), dtype=torch.uint8, device=dev)
+    noise.device_image_noise(image, region=ones)
+    region_ms = [round(timed(lambda: noise.device_image_noise(image, region=ones))[0], 3) for _ in range(args.repeat)]
+    del ones
+    host = image.cpu().numpy().ravel()
+    rank = (host.size - 1) // 2
+    median, reads_median = _select_replay(host, rank)
+    mad, reads_mad = _select_replay(np.abs(host - median), rank)
+    del host
+    bytes_read = 8.0 * n * n * (reads_median + reads_mad)
+    other = torch.empty_like(image)
+    other.copy_(image)
+    copy_ms = min(timed(lambda: other.copy_(image))[0] for _ in range(args.repeat))
+    del other
+    noise_and_mask(image)
+    mask_ms, rounds, minfo = [], None, None
+    for _ in range(args.repeat):
+        t, (_, minfo) = timed(lambda: noise.device_auto_mask(image, 5.0 * got["sigma"], 3.0 * got["sigma"]))
+        mask_ms.append(round(t, 3))
+    result = {
+        "data": f"the scene of --mode clean at {n}^2 ({args.sources} lognormal sources, {min(args.patch, n)}^2 PSF patch) "
+                f"plus seeded Gaussian pixel noise of sigma {args.noise_sigma}",
+        "npix": n, "repeat": args.repeat, "noise": got,
+        "metric": "ms per device_image_noise call (median + MAD of an fp64 image), best of repeats",
+        "value": min(hip_ms), "unit": "ms",
+        "device_image_noise_ms": hip_ms, "torch_kthvalue_pair_ms": torch_ms,
+        "device_image_noise_with_region_of_ones_ms": region_ms,
+        "spread_ms": {"device_image_noise": round(max(hip_ms) - min(hip_ms), 3),
+                      "torch_kthvalue_pair": round(max(torch_ms) - min(torch_ms), 3)},
+        "speedup_over_torch_kthvalue_pair": round(min(torch_ms) / min(hip_ms), 2),
+        "equal_to_torch": bool(got["median"] == ref[0] and got["mad"] == ref[1]),
+        "equal_to_numpy_replay": bool(got["median"] == median and got["mad"] == mad),
+        "full_image_reads": {"median": reads_median, "mad": reads_mad},
+        "GBs_at_8B_per_pixel_per_read": round(bytes_read / min(hip_ms) / 1e6, 1),
+        "device_copy_ms": round(copy_ms, 3), "device_copy_GBs_read_plus_write": round(16.0 * n * n / copy_ms / 1e6, 1),
+        "auto_mask_5_3_ms": mask_ms, "auto_mask": minfo,
+    }
+    del image
+    # one major cycle at C3: the predict of a model image and the re-invert through the first invert's plan
+    cfg = bench.CONFIGS[args.config]
+    uvw, freq, vis, wgt, px, _, _ = bench.make_inputs(cfg, 0, 1, dev)
+    m = cfg["npix"]
+    kw = dict(support=8, do_wstacking=False)
+    residual, _ = gridder.device_ms2dirty(uvw, freq, vis, wgt, m, m, px, px, normalise=True, **kw)
+    model = torch.zeros((m, m), dtype=torch.float64, device=dev)
+    model.view(-1)[torch.from_numpy(np.random.default_rng(3).choice(m * m, 1000, replace=False)).to(dev)] = 1.0
+
+    def cycle():
+        vres = predict.device_residual(uvw, freq, vis, model, px, None, reuse_plan=True, **kw)
+        gridder.device_ms2dirty(uvw, freq, vres, wgt, m, m, px, px, normalise=True, reuse_plan=True, out=residual, **kw)
+
+    cycle()
+    cycle_ms = min(timed(cycle)[0] for _ in range(args.repeat))
+    del uvw, vis, wgt, model
+    image = scene(m)
+    noise_and_mask(image)
+    both_ms = min(timed(lambda: noise_and_mask(image))[0] for _ in range(args.repeat))
+    result["major_cycle"] = {
+        "config": args.config, "npix": m, "visibilities": cfg["rows"] * cfg["nchan"],
+        "predict_plus_reinvert_ms": round(cycle_ms, 2), "noise_plus_mask_ms": round(both_ms, 3),
+        "noise_plus_mask_share_of_cycle": round(both_ms / cycle_ms, 4)}
+    path = ROOT / "profiles" / f"noise_{args.config}.json"
+    path.write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "ms_clean", "weights",
-                                      "restore", "gaincal", "dft"), required=True)
+                                      "restore", "gaincal", "dft", "noise"), required=True)
     ap.add_argument("--config", default="c3", help="weights / restore / gaincal / dft: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
@@ -893,6 +1061,8 @@ def main():
     ap.add_argument("--widths", type=float, nargs="+", default=[0.0, 4.0, 8.0, 16.0],
                     help="ms_clean: scale FWHMs in pixels")
     ap.add_argument("--full-niter", type=int, default=200, help="ms_clean: iterations of the full-PSF case at most")
+    ap.add_argument("--noise-npix", type=int, default=8192, help="noise: image edge")
+    ap.add_argument("--noise-sigma", type=float, default=0.05, help="noise: sigma of the added pixel noise")
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
 
@@ -914,6 +1084,9 @@ def main():
         return
     if args.mode == "dft":
         print(json.dumps(dft(args)), flush=True)
+        return
+    if args.mode == "noise":
+        print(json.dumps(noise_rows(args)), flush=True)
         return
     if args.mode == "mfs_clean":
         print(json.dumps(mfs_clean(args)), flush=True)
