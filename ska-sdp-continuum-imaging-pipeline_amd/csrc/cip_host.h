@@ -228,6 +228,7 @@ int scatter_tile_force();
 bool grid_f32_enabled();
 bool wacc_f32_enabled();
 bool fft_rowskip();
+bool mosaic_lds();
 
 struct Prepared {
   cip_gridder_params p;

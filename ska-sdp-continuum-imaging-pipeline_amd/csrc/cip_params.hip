@@ -399,6 +399,9 @@ int scatter_tile_force() {
   }();
   return v;
 }
+// CIP_MOSAIC_LDS=0: cip_mosaic_add reads the facet directly instead of staging
+// each tile's window in LDS (cip_mosaic.hip; A/B and the path test); read per call
+bool mosaic_lds() { return env_on("CIP_MOSAIC_LDS"); }
 #undef CIP_SWITCH
 
 // the HBM layout of the uv grid the FFT stage expects: gT[y, x] when the

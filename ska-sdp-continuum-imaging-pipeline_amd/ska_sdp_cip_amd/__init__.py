@@ -14,7 +14,8 @@ clean beam and the restored image (`restore.py`, `cip_beam_fit`,
 `cip_ms_clean`), antenna gain self-calibration (`calibrate.py`, `cip_gaincal`), the sky-model
 predict (`skymodel.py`, `cip_dft_predict`), the image noise and the island
 mask behind the major cycles' `auto_threshold` and `auto_mask` (`noise.py`,
-`cip_image_noise`, `cip_auto_mask`) and the `uvw_tiling` package.
+`cip_image_noise`, `cip_auto_mask`), facet mosaicking onto one wide-field
+plane (`mosaic.py`, `cip_mosaic_add`) and the `uvw_tiling` package.
 """
 
 __version__ = "0.1.0"
@@ -79,6 +80,8 @@ from .calibrate import (  # noqa: E402
 )
 from . import skymodel  # noqa: E402
 from .skymodel import SkyModel, device_dft_predict, dft_predict  # noqa: E402
+from . import mosaic  # noqa: E402
+from .mosaic import MosaicAccumulator, device_mosaic, facet_layout, mosaic_beta, mosaic_taps  # noqa: E402
 from .measurement_set import (  # noqa: E402
     InMemoryMeasurementSet,
     MeasurementSetReader,
@@ -163,4 +166,10 @@ __all__ = [
     "device_auto_mask",
     "image_noise",
     "auto_mask",
+    "mosaic",
+    "MosaicAccumulator",
+    "device_mosaic",
+    "facet_layout",
+    "mosaic_beta",
+    "mosaic_taps",
 ]

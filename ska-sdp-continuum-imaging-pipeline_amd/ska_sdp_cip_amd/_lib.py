@@ -1,7 +1,7 @@
 """
 ctypes binding of libcip_hip.so (C ABI: include/cip.h, include/cip_restore.h,
-include/cip_mfs.h, include/cip_cal.h, include/cip_dft.h, include/cip_ms.h and
-include/cip_noise.h).
+include/cip_mfs.h, include/cip_cal.h, include/cip_dft.h, include/cip_ms.h,
+include/cip_noise.h and include/cip_mosaic.h).
 
 The library is the product: there is no CPU fallback. `lib()` raises when the
 shared object is missing or cannot be loaded, and every call maps a negative
@@ -374,6 +374,41 @@ NOISE_PROTOTYPES = {
 }
 
 
+class MosaicGeom(ctypes.Structure):
+    """Mirror of `cip_mosaic_geom` (include/cip_mosaic.h)."""
+
+    _fields_ = [
+        ("nx", ctypes.c_int64),
+        ("ny", ctypes.c_int64),
+        ("px", ctypes.c_double),
+        ("py", ctypes.c_double),
+        ("fnx", ctypes.c_int64),
+        ("fny", ctypes.c_int64),
+        ("fpx", ctypes.c_double),
+        ("fpy", ctypes.c_double),
+        ("half", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("beta", ctypes.c_double),
+        ("trim", ctypes.c_int64),
+        ("feather", ctypes.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain-dict view."""
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# And for include/cip_mosaic.h, the eighth (the geometry, beta_out, taps_out and n_uncovered_out are HOST memory).
+MOSAIC_MAX_HALF = 8  # CIP_MOSAIC_MAX_HALF
+MOSAIC_NSCALE = 1  # CIP_MOSAIC_NSCALE
+MOSAIC_PROTOTYPES = {
+    "cip_mosaic_beta": (_i32, [_i32, _f64, _pf64]),
+    "cip_mosaic_taps": (_i32, [_i32, _f64, _f64, _pf64]),
+    "cip_mosaic_add": (_i32, [ctypes.POINTER(MosaicGeom), _vp, _i64, _f64, _f64, _vp, _vp, _vp]),
+    "cip_mosaic_finish": (_i32, [_vp, _vp, _i64, _i64, _i64, _f64, _vp, _pi64]),
+}
+
+
 def lib() -> ctypes.CDLL:
     """Load (once) and return the HIP library; raises if it is unavailable."""
     global _LIB  # pylint: disable=global-statement
@@ -389,7 +424,7 @@ def lib() -> ctypes.CDLL:
     so = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in (*PROTOTYPES.items(), *RESTORE_PROTOTYPES.items(), *MFS_PROTOTYPES.items(),
                                       *CAL_PROTOTYPES.items(), *DFT_PROTOTYPES.items(), *MS_PROTOTYPES.items(),
-                                      *NOISE_PROTOTYPES.items()):
+                                      *NOISE_PROTOTYPES.items(), *MOSAIC_PROTOTYPES.items()):
         fn = getattr(so, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = so

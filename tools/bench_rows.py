@@ -84,6 +84,22 @@ Secondary measurements of the SURVEY.md 8(f) rows built beside the hot path
                     cycle's predict + re-invert on bench.py's C3 inputs, with
                     the noise and the mask at C3's image size beside it; also
                     written to profiles/noise_c3.json
+  --mode mosaic     the facet mosaic (mosaic.py, cip_mosaic_add) at C5's size:
+                    --facets-xy (8 4) facets of --mosaic-facet^2 (4096) pixels
+                    with --mosaic-planes (4) planes at C5's pixel size onto the
+                    largest plane for which `facet_layout` places that grid,
+                    half-width --mosaic-half (6): ms per `add` (best and
+                    median over the facets of the best of --repeat mosaics),
+                    ms for the whole mosaic (the adds and `finish`), with the
+                    tile windows staged in LDS and with direct loads
+                    (CIP_MOSAIC_LDS), the two alternating in the same run;
+                    the traffic floor (each facet read once, the footprint's
+                    num and wsum read and written once) and the GB/s and the
+                    fraction of a device copy's rate that implies; the fp64
+                    fused multiply-adds of the tap sums per second; the same
+                    adds with one plane, which splits an add into the part per
+                    plane and the geometry and taps; also written to
+                    profiles/mosaic_c5.json
 
 Each prints one JSON line (synthetic data: real uvw tracks, random values).
 """
@@ -1030,10 +1046,113 @@ def noise_rows(args):
     return result
 
 
+def mosaic_rows(args):
+    """ms per MosaicAccumulator.add and per mosaic at C5's size, LDS staging against direct loads, beside the traffic floor."""
+    import os
+
+    import torch
+
+    from ska_sdp_cip_amd import synthetic as syn
+    from ska_sdp_cip_amd.mosaic import MosaicAccumulator, facet_layout
+
+    dev = torch.device("cuda", 0)
+    fx, fy = args.facets_xy or (8, 4)
+    fn, half, nplane = args.mosaic_facet, args.mosaic_half, args.mosaic_planes
+    # C5's pixel size (tests/test_gpu_c5.py): C3's tracks imaged on 4096^2 facets
+    uvw = syn.uvw_tracks(390_625, 64, array_radius_m=4000.0, seed=20241008)
+    freq = syn.channel_frequencies(256)
+    px = syn.pixel_size_for_grid(uvw, freq, 4096, support=8)
+    nu_max = float(np.abs(uvw[:, :2]).max() * freq.max() / syn.SPEED_OF_LIGHT * px)
+    del uvw
+    # the largest plane that `facet_layout` covers with fx x fy such facets
+    span = fn - 2 * half + 1
+    nx, ny = fx * span, fy * span
+    while len(centres := facet_layout(nx, ny, px, fn, half=half)) != fx * fy:
+        nx, ny = nx - fx, ny - fy
+    g = torch.Generator(device=dev)
+    g.manual_seed(20241022)
+    facet = torch.randn((nplane, fn, fn), dtype=torch.float64, device=dev, generator=g)
+
+    def timed(fn_):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn_()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def one_mosaic(lds, planes=nplane):
+        os.environ["CIP_MOSAIC_LDS"] = "1" if lds else "0"
+        acc = MosaicAccumulator(nx, ny, px, px, planes, half=half, nu_max=nu_max)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        adds = [timed(lambda c=c: acc.add(facet[:planes], c[0], c[1]))[0] for c in centres]
+        covered = float(acc.wsum.sum())  # feather 0: every weight is 1, so this counts the pixels the adds wrote
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        _, missed = acc.finish()
+        torch.cuda.synchronize()
+        return {"adds_ms": adds, "finish_ms": (time.perf_counter() - t1) * 1e3,
+                "mosaic_ms": sum(adds) + (time.perf_counter() - t1) * 1e3, "covered": covered, "uncovered": missed,
+                "wall_ms": (time.perf_counter() - t0) * 1e3}
+
+    one_mosaic(True)  # warm-up: both kernels' code objects, the allocator
+    one_mosaic(False)
+    runs = {True: [], False: []}
+    for _ in range(args.repeat):
+        for lds in (True, False):
+            runs[lds].append(one_mosaic(lds))
+    # one plane: what an add costs before any plane's tap sums (the geometry and the taps) and per plane
+    one_mosaic(True, 1)
+    single = min(sum(one_mosaic(True, 1)["adds_ms"]) for _ in range(args.repeat)) / len(centres)
+    os.environ.pop("CIP_MOSAIC_LDS", None)
+    src = torch.empty((nx * ny,), dtype=torch.float64, device=dev)
+    dst = torch.empty_like(src)
+    copy_ms = min(timed(lambda: dst.copy_(src))[0] for _ in range(args.repeat + 1))
+    copy_gbs = 2 * src.numel() * 8 / copy_ms / 1e6
+    del src, dst
+    covered = runs[True][0]["covered"]
+    facet_bytes = nplane * fn * fn * 8
+    # each facet read once; num (nplane) and wsum of the footprint read and written once
+    floor_bytes = len(centres) * facet_bytes + covered * (nplane + 1) * 16
+    fma = covered * nplane * 4 * half * half
+
+    def summary(rs):
+        best = min(rs, key=lambda r: sum(r["adds_ms"]))
+        adds_ms = sum(best["adds_ms"])
+        return {"add_ms_best": round(min(best["adds_ms"]), 3), "add_ms_median": round(float(np.median(best["adds_ms"])), 3),
+                "adds_ms_total": round(adds_ms, 2), "finish_ms": round(min(r["finish_ms"] for r in rs), 2),
+                "mosaic_ms": round(min(r["mosaic_ms"] for r in rs), 2),
+                "adds_ms_total_all_repeats": [round(sum(r["adds_ms"]), 2) for r in rs],
+                "floor_GBs": round(floor_bytes / adds_ms / 1e6, 1),
+                "fraction_of_copy_rate": round(floor_bytes / adds_ms / 1e6 / copy_gbs, 3),
+                "tap_sum_fp64_TFMAs": round(fma / adds_ms / 1e9, 2)}
+
+    result = {
+        "data": "standard-normal facet planes (pure resampling: the values do not matter)",
+        "facets": [fx, fy], "facet_pixels": fn, "planes": nplane, "half": half, "plane": [nx, ny],
+        "pixel_size": px, "field_rad": [round(nx * px, 4), round(ny * px, 4)], "nu_max": round(nu_max, 4),
+        "repeat": args.repeat, "uncovered": runs[True][0]["uncovered"],
+        "metric": "ms per MosaicAccumulator.add (one facet, all planes), synchronised around each call",
+        "covered_pixels_over_all_adds": covered, "traffic_floor_bytes": floor_bytes,
+        "traffic_floor": "each facet read once + read and write of the footprint's num and wsum",
+        "tap_sum_fma": fma, "device_copy_GBs": round(copy_gbs, 1),
+        "lds_staging": summary(runs[True]), "direct_loads": summary(runs[False]),
+    }
+    if nplane > 1:
+        mean = result["lds_staging"]["adds_ms_total"] / len(centres)
+        per_plane = (mean - single) / (nplane - 1)
+        result["plane_scaling_lds"] = {"add_ms_mean": round(mean, 3), "add_ms_mean_one_plane": round(single, 3),
+                                       "ms_per_plane": round(per_plane, 3),
+                                       "ms_geometry_and_taps": round(single - per_plane, 3)}
+    path = ROOT / "profiles" / "mosaic_c5.json"
+    path.write_text(json.dumps(result, indent=1) + "\n")
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("stream", "continuum", "degrid", "clean", "mfs_clean", "ms_clean", "weights",
-                                      "restore", "gaincal", "dft", "noise"), required=True)
+                                      "restore", "gaincal", "dft", "noise", "mosaic"), required=True)
     ap.add_argument("--config", default="c3", help="weights / restore / gaincal / dft: the bench.py configuration whose inputs are used")
     ap.add_argument("--rows", type=int, default=156_250)
     ap.add_argument("--nchan", type=int, default=64)
@@ -1063,6 +1182,9 @@ def main():
     ap.add_argument("--full-niter", type=int, default=200, help="ms_clean: iterations of the full-PSF case at most")
     ap.add_argument("--noise-npix", type=int, default=8192, help="noise: image edge")
     ap.add_argument("--noise-sigma", type=float, default=0.05, help="noise: sigma of the added pixel noise")
+    ap.add_argument("--mosaic-facet", type=int, default=4096, help="mosaic: facet edge")
+    ap.add_argument("--mosaic-planes", type=int, default=4, help="mosaic: planes per facet")
+    ap.add_argument("--mosaic-half", type=int, default=6, help="mosaic: taps either side")
     ap.add_argument("--no-reuse", action="store_true", help="continuum: plan every product (no CIP_REUSE_PLAN)")
     args = ap.parse_args()
 
@@ -1087,6 +1209,9 @@ def main():
         return
     if args.mode == "noise":
         print(json.dumps(noise_rows(args)), flush=True)
+        return
+    if args.mode == "mosaic":
+        print(json.dumps(mosaic_rows(args)), flush=True)
         return
     if args.mode == "mfs_clean":
         print(json.dumps(mfs_clean(args)), flush=True)
