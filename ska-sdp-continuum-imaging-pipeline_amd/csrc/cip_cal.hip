@@ -172,13 +172,6 @@ __device__ __forceinline__ double max_abs4(double a, double b, double c, double 
   return fmax(fmax(fabs(a), fabs(b)), fmax(fabs(c), fabs(d)));
 }
 
-template <typename T>
-__device__ __forceinline__ T cal_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // Workgroup b takes the row blocks b, b + gridDim, ... of kCalThreads / L rows each (nblk in all); in a block,
 // thread t has row t / L and is lane t % L of it, channels [kCalRun (l + L j), + kCalRun) for j = 0, 1, ...
 // The counts and the maxima stay in registers over the row blocks, so the few words every workgroup
@@ -260,12 +253,10 @@ __global__ __launch_bounds__(kCalThreads) void cal_correlate_kernel(const VC* __
       }
     }
     if constexpr (MODE == CAL_ADD) {
-      // the group's sums in its lead lane: a lane past the group's end is only ever read by non-lead lanes
-      for (int off = L >> 1; off > 0; off >>= 1) {
-        s0 += __shfl_down(s0, off, 64);
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-      }
+      // the group's sums in its lead lane
+      s0 = wave_sum(s0, L);
+      s1 = wave_sum(s1, L);
+      s2 = wave_sum(s2, L);
       if (l == 0 && row_ok && (s0 | s1 | s2) != 0) {
         unsigned long long* cell = corr + (((int64_t)s * a.n_ant + p) * a.n_ant + q) * 3;
         atomicAdd(cell, (unsigned long long)s0);
@@ -289,8 +280,8 @@ __global__ __launch_bounds__(kCalThreads) void cal_correlate_kernel(const VC* __
     // four integer adds per workgroup
     __shared__ unsigned long long s_cnt[kCalThreads / 64][4];
     using u64 = unsigned long long;
-    const u64 c_add = cal_wave_sum((u64)n_add), c_zero = cal_wave_sum((u64)n_zero);
-    const u64 c_out = cal_wave_sum((u64)n_out), c_bad = cal_wave_sum((u64)n_bad);
+    const u64 c_add = wave_sum((u64)n_add), c_zero = wave_sum((u64)n_zero);
+    const u64 c_out = wave_sum((u64)n_out), c_bad = wave_sum((u64)n_bad);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
       s_cnt[wave][0] = c_add;
@@ -690,17 +681,15 @@ CalRows make_rows(int64_t nrow, int64_t nchan, const int32_t* ant1, const int32_
   return a;
 }
 
-constexpr size_t kCalStaging = 64;  // bytes of pinned staging the count and max readbacks take
-
-// host: pinned staging of >= kCalStaging bytes. Waits for the stream once.
+// Waits for the stream once.
 int correlate_run(Workspace* ws, hipStream_t s, const CalColumns& c, const CalRows& a, const cip_cal_scale& sc,
-                  int64_t* corr, int64_t* host, cip_cal_counts* counts_out) {
+                  int64_t* corr, cip_cal_counts* counts_out) {
   CIP_ALLOC(counts, unsigned long long, "cal_counts", 4)
   CIP_HIP_CHECK(hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), s));
   const CalBounds b = {sc.amax, sc.wmax, sc.shift};
   CIP_HIP_CHECK(launch_correlate<CAL_ADD>(c, a, b, corr, counts, s));
-  CIP_HIP_CHECK(hipMemcpyAsync(host, counts, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  int64_t* host = nullptr;
+  if (const int rc = readback(ws, s, {{counts, 4 * sizeof(int64_t)}}, &host); rc != CIP_OK) return rc;
   if (counts_out) *counts_out = {host[0], host[1], host[2], host[3]};
   return CIP_OK;
 }
@@ -715,8 +704,6 @@ int solve_run(Workspace* ws, hipStream_t s, const int64_t* corr, const cip_cal_s
   CIP_ALLOC(ai, double, "cal_a_im", total)
   CIP_ALLOC(bb, double, "cal_b", total)
   CIP_ALLOC(stat, SolveStat, "cal_stat", sc.n_int)
-  SolveStat* host = (SolveStat*)pinned(ws, std::max(kCalStaging, (size_t)sc.n_int * sizeof(SolveStat)));
-  if (!host) return CIP_ENOMEM;
   cal_expand_kernel<<<dim3((unsigned)((total + kCalThreads - 1) / kCalThreads)), dim3(kCalThreads), 0, s>>>(
       (const long long*)corr, total, (int)n, sc.quantum, ar, ai, bb);
   CIP_HIP_CHECK(hipGetLastError());
@@ -725,8 +712,8 @@ int solve_run(Workspace* ws, hipStream_t s, const int64_t* corr, const cip_cal_s
       ar, ai, bb, (int)n, (long long)niter, tol * tol, (int)refant, (flags & CIP_CAL_PHASE_ONLY) ? 1 : 0,
       (double2*)gains, ant_ok, (long long*)iters_out, stat);
   CIP_HIP_CHECK(hipGetLastError());
-  CIP_HIP_CHECK(hipMemcpyAsync(host, stat, (size_t)sc.n_int * sizeof(SolveStat), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  SolveStat* host = nullptr;
+  if (const int rc = readback(ws, s, {{stat, (size_t)sc.n_int * sizeof(SolveStat)}}, &host); rc != CIP_OK) return rc;
   cip_cal_solve_info info = {0, 0, 0, 0, 0.0};
   for (int64_t i = 0; i < sc.n_int; ++i) {
     const SolveStat& st = host[i];
@@ -754,11 +741,9 @@ int correlate_impl(const CalColumns& c, int64_t nrow, int64_t nchan, const int32
   if (nrow == 0) return CIP_OK;
   if (!corr) return set_error(CIP_EINVAL, "cip_cal_correlate: corr_io must not be NULL");
   CIP_BEGIN_CALL(hip_stream, false)
-  int64_t* host = (int64_t*)pinned(ws, kCalStaging);
-  if (!host) return CIP_ENOMEM;
   const CalRows a = make_rows(nrow, nchan, ant1, ant2, interval, sc->n_ant, sc->n_int,
                               aligned16(c.vis) && aligned16(c.model) && aligned16(c.wgt));
-  return correlate_run(ws, s, c, a, *sc, corr, host, counts_out);
+  return correlate_run(ws, s, c, a, *sc, corr, counts_out);
 }
 
 int solve_impl(const int64_t* corr, const cip_cal_scale* sc, int64_t niter, double tol, int64_t refant, int flags,
@@ -810,8 +795,6 @@ int gaincal_impl(const CalColumns& c, int64_t nrow, int64_t nchan, const int32_t
   if (const int rc = columns_check(who, c, nrow); rc != CIP_OK) return rc;
   if (const int rc = solve_check(who, n_ant, niter, tol, refant, flags, gains, ant_ok); rc != CIP_OK) return rc;
   CIP_BEGIN_CALL(hip_stream, false)
-  int64_t* host = (int64_t*)pinned(ws, kCalStaging);
-  if (!host) return CIP_ENOMEM;
   const CalRows a = make_rows(nrow, nchan, ant1, ant2, interval, n_ant, n_int,
                               aligned16(c.vis) && aligned16(c.model) && aligned16(c.wgt));
   double amax = 0.0, wmax = 0.0;
@@ -819,8 +802,8 @@ int gaincal_impl(const CalColumns& c, int64_t nrow, int64_t nchan, const int32_t
     CIP_ALLOC(mx, unsigned long long, "cal_max", 2)
     CIP_HIP_CHECK(hipMemsetAsync(mx, 0, 2 * sizeof(unsigned long long), s));
     CIP_HIP_CHECK(launch_correlate<CAL_MAX>(c, a, CalBounds{0.0, 0.0, 0}, nullptr, mx, s));
-    CIP_HIP_CHECK(hipMemcpyAsync(host, mx, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t* host = nullptr;
+    if (const int rc = readback(ws, s, {{mx, 2 * sizeof(int64_t)}}, &host); rc != CIP_OK) return rc;
     std::memcpy(&amax, &host[0], sizeof(double));
     std::memcpy(&wmax, &host[1], sizeof(double));
   }
@@ -835,7 +818,7 @@ int gaincal_impl(const CalColumns& c, int64_t nrow, int64_t nchan, const int32_t
   CIP_HIP_CHECK(hipMemsetAsync(corr, 0, (size_t)ncorr * sizeof(int64_t), s));
   if (counts_out) *counts_out = {0, 0, 0, 0};
   if (nrow > 0)
-    if (const int rc = correlate_run(ws, s, c, a, sc, corr, host, counts_out); rc != CIP_OK) return rc;
+    if (const int rc = correlate_run(ws, s, c, a, sc, corr, counts_out); rc != CIP_OK) return rc;
   return solve_run(ws, s, corr, sc, niter, tol, refant, flags, gains, ant_ok, iters_out, info_out);
 }
 

@@ -479,7 +479,7 @@ struct CycleHost {
 // the tile table, then select and (subtract, select) pairs are queued `batch`
 // iterations at a time; the device state is read back once per batch. Kernels
 // queued behind a stop return at once, so the result does not depend on `batch`.
-// Returns the final state in *final (pinned staging: read it before the next call).
+// Returns the final state in *final (readback()'s staging: read it before the next call).
 int clean_impl(const char* entry, const CycleHost& cyc, double* res, int64_t nx, int64_t ny, const double* psf,
                int64_t px, int64_t py, int64_t cx, int64_t cy, const uint8_t* mask, double gain, double threshold,
                int64_t niter, int64_t batch, void* hip_stream, double* model, int64_t* comp_index, double* comp_flux,
@@ -521,8 +521,7 @@ int clean_impl(const char* entry, const CycleHost& cyc, double* res, int64_t nx,
   CIP_BEGIN_CALL(hip_stream, false)
   CIP_ALLOC(table, CleanEntry, "clean_table", ntiles)
   CIP_ALLOC(state, CleanState, "clean_state", 1)
-  CleanState* h = (CleanState*)pinned(ws, sizeof(CleanState));
-  if (!h) return CIP_ENOMEM;
+  CleanState* h = nullptr;
   CleanArgs a{};
   a.res = res, a.nx = nx, a.ny = ny, a.nty = (ny + kTY - 1) / kTY;
   a.psf = psf, a.px = px, a.py = py, a.cx = cx, a.cy = cy;
@@ -545,8 +544,7 @@ int clean_impl(const char* entry, const CycleHost& cyc, double* res, int64_t nx,
       CIP_HIP_CHECK(select());
     }
     queued += n;
-    CIP_HIP_CHECK(hipMemcpyAsync(h, state, sizeof(CleanState), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    if (const int rc = readback(ws, s, {{state, sizeof(CleanState)}}, &h); rc != CIP_OK) return rc;
     if (h->stopped) break;
     // after niter pairs the last select saw k == niter and stopped
     if (queued >= niter) return fail(CIP_EHIP, "the device state did not stop");

@@ -300,6 +300,19 @@ __device__ __forceinline__ void footprint(double x, int half_w, int64_t* i0, dou
   *y = 2.0 * (s - fl) - 1.0;
 }
 
+// The sum over each aligned group of `lanes` lanes (a power of two; 64: the
+// wave) in the group's lead lane, in a fixed order: __shfl_down over offsets
+// lanes / 2 ... 1. A lane past the group's end is only ever read by non-lead
+// lanes. (The planner's, the gridder's and the scatter's reductions keep their
+// own loops: their order and register counts are pinned by tests.)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v, int lanes = 64) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    if (off < lanes) v += __shfl_down(v, off, 64);
+  return v;
+}
+
 // i mod n in [0, n): one compare-and-add for |i| < 2n (all but absurd
 // coordinates), the 64-bit remainder only beyond that.
 __device__ __forceinline__ int64_t wrap_index(int64_t i, int64_t n) {

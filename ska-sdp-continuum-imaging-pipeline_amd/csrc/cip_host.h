@@ -1,12 +1,14 @@
 // cip_host.h - what the host-side units of libcip_hip.so share (cip_workspace,
 // cip_params, cip_planner, cip_invert, cip_predict and the entry points kept
 // beside their launchers in cip_clean, cip_strips, cip_tiling): the per-thread
-// workspace, the planner's request and result, the call scope and the CIP_*
+// workspace with its cached host tables (host_table) and its one readback
+// (readback), the planner's request and result, the call scope and the CIP_*
 // switches. Host only and not part of the C ABI (include/cip.h is); units
 // that hold nothing but kernels and launchers include cip_internal.h alone.
 #pragma once
 #include <hipfft/hipfft.h>
 
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -92,15 +94,23 @@ struct PlanResult {
   int tx_shift = kTileShift, ty_shift = kTileShift;  // the work tile the plan was made on (GridGeometry's)
 };
 
+// A table the host computes and keeps on the device (host_table): the
+// grid-correction vectors, the w-correction table, the FFT twiddles of each
+// length, the restore taps and the multiscale taps.
+struct HostTable {
+  std::vector<double> key;  // what the device copy was made from; empty: none
+  void* staging = nullptr;  // pinned, this table's own (every readback rewrites `pinned`); grows like it
+  size_t staging_bytes = 0;
+  hipEvent_t uploaded = nullptr;  // behind the last upload: the next one waits for it before it refills the staging
+};
+
 struct Workspace {
   int device = 0;  // the device every buffer, stream and event belongs to
   std::map<std::string, DevBuf> bufs;
+  std::map<std::string, HostTable> tables;  // by name, as bufs
   std::vector<FftPlan> plans;
-  void* pinned = nullptr;  // small host staging
+  void* pinned = nullptr;  // small host staging: what the last readback (or pinned()) handed out
   size_t pinned_bytes = 0;
-  std::vector<int64_t> corr_key;  // (npix_x, npix_y, nu, nv, W) of the cached cx / cy
-  std::vector<double> fw_key;     // (W, dw |nmin|) of the cached w-correction table
-  std::vector<int64_t> tw_ready;  // lengths whose FFT twiddle tables are on the device
   // second stream: zeroes the first grid plane while the planner runs
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -127,7 +137,7 @@ struct Workspace {
   // a planner ran on a caller's stream (parity-0 buffer names) since the last
   // pipelined call: the next pipelined planner waits for that stream
   bool plan_unscoped = false;
-  // the stream of the last CIP_ASYNC call, whose work may still be queued: a
+  // the stream of the last call that left its work queued (leave_queued): a
   // call on another stream first waits for it (the workspace is shared)
   hipStream_t async_stream = nullptr;
   // the last complete plan (its buffers stay untouched until the next planner
@@ -138,18 +148,6 @@ struct Workspace {
   std::vector<double> saved_key;
   cip_gridder_params saved_p;
   PlanResult saved_plan;
-  // cip_restore never waits for the device, so its tap table goes up through
-  // pinned staging of its own (`pinned` is rewritten by the next call): the
-  // (a, b, c, R) of the table on the device, and the event behind the last
-  // upload, which the next upload waits for before it rewrites the staging
-  void* restore_pinned = nullptr;
-  hipEvent_t ev_restore = nullptr;
-  std::vector<double> restore_key;
-  // the same for cip_ms_convolve's 1-D scale taps: the table on the device is
-  // (R, taps[0 .. 2R])
-  void* ms_pinned = nullptr;
-  hipEvent_t ev_ms = nullptr;
-  std::vector<double> ms_key;
 };
 
 // ---- cip_workspace.hip ----
@@ -163,8 +161,41 @@ T* buf(Workspace* ws, const char* name, int64_t count) {
 #define CIP_ALLOC(var, T, name, n)  \
   T* var = buf<T>(ws, name, (n));   \
   if (!var) return CIP_ENOMEM;
-// small pinned host staging; returns nullptr (and sets the error) on failure
+// small pinned host staging; returns nullptr (and sets the error) on failure.
+// A larger request frees and reallocates it: the pointer holds until the next
+// pinned() or readback() on the workspace, so no function passes it on.
 void* pinned(Workspace* ws, size_t bytes);
+// A few scalars back on the host: sizes the staging once, copies every source
+// into consecutive 8-byte-aligned slots of it (a NULL source leaves its slot
+// unwritten), waits for s once. *host: the staging, under pinned()'s rule.
+struct DevSrc {
+  const void* dev;
+  size_t bytes;
+};
+int readback_bytes(Workspace* ws, hipStream_t s, std::initializer_list<DevSrc> src, void** host);
+template <typename T>
+int readback(Workspace* ws, hipStream_t s, std::initializer_list<DevSrc> src, T** host) {
+  return readback_bytes(ws, s, src, (void**)host);
+}
+// The two halves of host_table. open: *staging = NULL when the device copy was
+// made from `key`; else forgets the key, waits for the last upload to have read
+// the staging and hands out `bytes` of it. upload: staging -> dev on s, the
+// event behind it, and only then the key.
+int host_table_open(Workspace* ws, const char* name, const std::vector<double>& key, size_t bytes, void** staging);
+int host_table_upload(Workspace* ws, const char* name, const std::vector<double>& key, void* dev, size_t bytes,
+                      hipStream_t s);
+// dev: the table's device buffer (a CIP_ALLOC of the caller's), used in stream
+// order on s. Unless it was made from `key`: fill(staging), `bytes` to dev on
+// s. Never waits for the stream: a call on another stream waits in begin_call
+// for whatever this one leaves queued.
+template <typename Fill>
+int host_table(Workspace* ws, const char* name, const std::vector<double>& key, void* dev, size_t bytes,
+               hipStream_t s, Fill&& fill) {
+  void* staging = nullptr;
+  if (const int rc = host_table_open(ws, name, key, bytes, &staging); rc != CIP_OK || !staging) return rc;
+  fill(staging);
+  return host_table_upload(ws, name, key, dev, bytes, s);
+}
 int fft_plan(Workspace* ws, int64_t nu, int64_t nv, hipStream_t s, hipfftHandle* out);
 int fft_twiddles(Workspace* ws, int64_t n, hipStream_t s, double** out);
 int zero_on_side(Workspace* ws, void* p, size_t bytes, hipStream_t s);
@@ -185,6 +216,9 @@ struct Call {
 int begin_call(void* hip_stream, bool profiled, Call* c);
 // Closes span 5 (profiled calls), synchronises the stream, reads the profile.
 int end_call(const Call& c);
+// Instead of end_call: the call's work is only queued, so a later call on
+// another stream waits for this one before it touches the workspace (begin_call)
+void leave_queued(const Call& c);
 // the usual opening of an entry point, after its argument checks: declares
 // `call`, and `ws` and `s` as the bodies (and CIP_ALLOC) name them
 #define CIP_BEGIN_CALL(hip_stream, profiled)                                              \

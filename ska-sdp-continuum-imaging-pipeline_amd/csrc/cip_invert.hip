@@ -412,7 +412,7 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
   // of this thread in stream order, so nothing on the host waits for it; the
   // grid-clean mark holds in stream order too
   if (!(flags & CIP_ASYNC) || g_prof.on) CIP_HIP_CHECK(hipStreamSynchronize(s));
-  else ws->async_stream = s;
+  else leave_queued(call);
   if (clean) {
     ws->grid_clean = grid;
     ws->grid_clean_bytes = std::max(prev_clean, group_bytes);

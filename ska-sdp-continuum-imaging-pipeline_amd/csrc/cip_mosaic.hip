@@ -210,8 +210,7 @@ __global__ __launch_bounds__(kFinThreads) void mosaic_finish_kernel(double* __re
     miss += !on;
     for (int64_t p = 0; p < nplane; ++p) num[p * n + e] = on ? num[p * n + e] / ws : fill;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) miss += __shfl_down(miss, off);
+  miss = wave_sum(miss);
   if ((threadIdx.x & 63) == 0 && miss) atomicAdd(uncovered, (unsigned long long)miss);
 }
 
@@ -400,15 +399,13 @@ int finish_impl(double* num_io, const double* wsum, int64_t nplane, int64_t nx, 
   const int64_t n = nx * ny;
   CIP_BEGIN_CALL(hip_stream, false)
   CIP_ALLOC(count, unsigned long long, "mosaic_count", 1)
-  unsigned long long* h = (unsigned long long*)pinned(ws, sizeof(unsigned long long));
-  if (!h) return CIP_ENOMEM;
   const int64_t want = (n + kFinThreads - 1) / kFinThreads;
   const int blocks = (int)(want > kFinMaxBlocks ? kFinMaxBlocks : want);
   CIP_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
   mosaic_finish_kernel<<<dim3(blocks), dim3(kFinThreads), 0, s>>>(num_io, wsum, nplane, n, fill, count);
   CIP_HIP_CHECK(hipGetLastError());
-  CIP_HIP_CHECK(hipMemcpyAsync(h, count, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  unsigned long long* h = nullptr;
+  if (const int rc = readback(ws, s, {{count, sizeof(unsigned long long)}}, &h); rc != CIP_OK) return rc;
   *n_uncovered_out = (int64_t)*h;
   return CIP_OK;
 }

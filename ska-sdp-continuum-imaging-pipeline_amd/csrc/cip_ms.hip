@@ -177,27 +177,12 @@ int convolve_impl(const double* in, int64_t nx, int64_t ny, const double* taps, 
   CIP_ALLOC(dtaps, double, "ms_taps", kMaxTaps)
   std::vector<double> key(taps, taps + 2 * R + 1);
   key.push_back((double)R);
-  if (ws->ms_key != key) {
-    ws->ms_key.clear();
-    if (!ws->ms_pinned) {
-      if (hipHostMalloc(&ws->ms_pinned, sizeof(double) * kMaxTaps) != hipSuccess) {
-        ws->ms_pinned = nullptr;
-        return set_error(CIP_ENOMEM, "hipHostMalloc failed");
-      }
-      CIP_HIP_CHECK(hipEventCreateWithFlags(&ws->ev_ms, hipEventDisableTiming));
-    } else {
-      // the last upload has read the staging (it has, unless that stream is far behind)
-      CIP_HIP_CHECK(hipEventSynchronize(ws->ev_ms));
-    }
-    std::copy(taps, taps + 2 * R + 1, (double*)ws->ms_pinned);
-    CIP_HIP_CHECK(hipMemcpyAsync(dtaps, ws->ms_pinned, sizeof(double) * (size_t)(2 * R + 1), hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipEventRecord(ws->ev_ms, s));
-    ws->ms_key = key;
-  }
+  if (const int rc = host_table(ws, "ms_taps", key, dtaps, sizeof(double) * (size_t)(2 * R + 1), s,
+                                [&](void* staging) { std::copy(taps, taps + 2 * R + 1, (double*)staging); });
+      rc != CIP_OK)
+    return rc;
   CIP_HIP_CHECK(launch_convolve(in, nx, ny, (int)R, dtaps, tmp, out, s));
-  // the work is only queued: a later call on another stream waits for this one
-  // before it touches the workspace (begin_call)
-  ws->async_stream = s;
+  leave_queued(call);
   return CIP_OK;
 }
 

@@ -277,7 +277,7 @@ int select_run(Workspace* ws, hipStream_t s, const double* img, int64_t n, const
   SelectState* h = (SelectState*)pinned(ws, sizeof(SelectState));
   if (!h) return CIP_ENOMEM;
   *h = SelectState{0, (long long)rank, 0, 0, 0, 0};
-  // the staging is next written by the first pass's read-back, behind this copy on the stream
+  // the staging (the readbacks' own) is next written by the first pass's readback, behind this copy on the stream
   CIP_HIP_CHECK(hipMemcpyAsync(state, h, sizeof(SelectState), hipMemcpyHostToDevice, s));
   SelectSource src{img, region, nullptr, n, (int64_t)(((uintptr_t)img & 15u) ? 1 : 0), mode, centre};
   u64 himask = 0, prefix = 0;
@@ -292,8 +292,7 @@ int select_run(Workspace* ws, hipStream_t s, const double* img, int64_t n, const
     CIP_HIP_CHECK(hipGetLastError());
     select_scan_kernel<<<dim3(1), dim3(256), 0, s>>>(hist, nbins, shift, pass == 0, state);
     CIP_HIP_CHECK(hipGetLastError());
-    CIP_HIP_CHECK(hipMemcpyAsync(h, state, sizeof(SelectState), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    if (const int rc = readback(ws, s, {{state, sizeof(SelectState)}}, &h); rc != CIP_OK) return rc;
     if (pass == 0) *count = h->count;
     if (h->status) {
       *found = false;
@@ -378,8 +377,7 @@ struct MaskSmall {
 
 // the wave's sum of v, added to *dst by one lane
 __device__ __forceinline__ void wave_count(u64* dst, unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (u64)v);
 }
 
@@ -493,8 +491,7 @@ int auto_mask_impl(const double* image, int64_t nx, int64_t ny, double seed, dou
   CIP_ALLOC(state, uint8_t, "mask_state", n)
   CIP_ALLOC(dirty, uint8_t, "mask_tiles", 2 * ntx * nty)  // the tiles a round works on, and the next round's
   CIP_ALLOC(small, MaskSmall, "mask_small", 1)
-  MaskSmall* h = (MaskSmall*)pinned(ws, sizeof(MaskSmall));
-  if (!h) return CIP_ENOMEM;
+  MaskSmall* h = nullptr;
   const int64_t want = (n + kMaskThreads - 1) / kMaskThreads;
   const int blocks = (int)(want > kMaskMaxBlocks ? kMaskMaxBlocks : want);
   CIP_HIP_CHECK(hipMemsetAsync(small, 0, sizeof(MaskSmall), s));
@@ -514,14 +511,12 @@ int auto_mask_impl(const double* image, int64_t nx, int64_t ny, double seed, dou
       CIP_HIP_CHECK(hipGetLastError());
     }
     rounds += kMaskRoundsPerCheck;
-    CIP_HIP_CHECK(hipMemcpyAsync(h, small, sizeof(MaskSmall), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    if (const int rc = readback(ws, s, {{small, sizeof(MaskSmall)}}, &h); rc != CIP_OK) return rc;
     if (!h->changed[kMaskRoundsPerCheck - 1]) break;  // and so would every later round
   }
   mask_final_kernel<<<dim3(blocks), dim3(kMaskThreads), 0, s>>>(state, base, n, mask_out, small);
   CIP_HIP_CHECK(hipGetLastError());
-  CIP_HIP_CHECK(hipMemcpyAsync(h, small, sizeof(MaskSmall), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  if (const int rc = readback(ws, s, {{small, sizeof(MaskSmall)}}, &h); rc != CIP_OK) return rc;
   out->n_seed = (int64_t)h->n_seed;
   out->n_island = (int64_t)h->n_island;
   out->n_out = (int64_t)h->n_out;

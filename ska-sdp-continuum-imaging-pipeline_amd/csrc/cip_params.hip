@@ -222,19 +222,16 @@ int correction_vectors(Workspace* ws, const GridGeometry& g, int64_t npix_x, int
   HostKernel hk;
   host_kernel(g.support, &hk);
   KernelFT F(hk);
-  // the correction vectors depend only on (npix, grid, W): cache them per device
-  const std::vector<int64_t> corr_key = {npix_x, npix_y, g.nu, g.nv, g.support};
-  if (ws->corr_key != corr_key) {
-    ws->corr_key.clear();
-    std::vector<double> hx(npix_x), hy(npix_y);
-    for (int64_t i = 0; i < npix_x; ++i) hx[i] = 1.0 / F((double)(i - npix_x / 2) / (double)g.nu);
-    for (int64_t j = 0; j < npix_y; ++j) hy[j] = 1.0 / F((double)(j - npix_y / 2) / (double)g.nv);
-    CIP_HIP_CHECK(hipMemcpyAsync(cx, hx.data(), sizeof(double) * npix_x, hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipMemcpyAsync(cy, hy.data(), sizeof(double) * npix_y, hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));  // host vectors go out of scope
-    ws->corr_key = corr_key;
-  }
-  return CIP_OK;
+  // each vector depends only on its (npix, grid length, W): one cached table per axis
+  const auto axis = [&](const char* name, double* dev, int64_t npix, int64_t n) {
+    return host_table(ws, name, {(double)npix, (double)n, (double)g.support}, dev, sizeof(double) * npix, s,
+                      [&](void* staging) {
+                        double* h = (double*)staging;
+                        for (int64_t i = 0; i < npix; ++i) h[i] = 1.0 / F((double)(i - npix / 2) / (double)n);
+                      });
+  };
+  if (const int rc = axis("cx", cx, npix_x, g.nu); rc != CIP_OK) return rc;
+  return axis("cy", cy, npix_y, g.nv);
 }
 
 // the w-stacking final correction's table of F (cached per workspace)
@@ -247,19 +244,13 @@ int w_correction_table(Workspace* ws, const cip_gridder_params& prm, const GridG
   const double numax = g.dw * std::fabs(prm.nmin);
   const double dnu = (numax > 0 ? numax : 1e-3) * 1.0001 / 4096.0;
   CIP_ALLOC(fwd, double, "fw_table", fw_n)
-  const std::vector<double> fw_key = {(double)g.support, numax};
-  if (ws->fw_key != fw_key) {
-    ws->fw_key.clear();
-    std::vector<double> fw(fw_n);
-    for (int64_t k = 0; k < fw_n; ++k) fw[k] = F((double)k * dnu);
-    CIP_HIP_CHECK(hipMemcpyAsync(fwd, fw.data(), sizeof(double) * fw_n, hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
-    ws->fw_key = fw_key;
-  }
   *table = fwd;
   *n = fw_n;
   *dnu_out = dnu;
-  return CIP_OK;
+  return host_table(ws, "fw_table", {(double)g.support, numax}, fwd, sizeof(double) * fw_n, s, [&](void* staging) {
+    double* fw = (double*)staging;
+    for (int64_t k = 0; k < fw_n; ++k) fw[k] = F((double)k * dnu);
+  });
 }
 
 // w planes per scatter work unit in w-stacking mode: G = 3 (a visibility

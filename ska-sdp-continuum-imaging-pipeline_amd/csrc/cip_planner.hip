@@ -87,12 +87,11 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
   CIP_HIP_CHECK(launch_prep_final(partial, nblk, red, s));
   CIP_HIP_CHECK(launch_radix_group_hist(hist0, nblk, g0, hist0g, s));
   CIP_HIP_CHECK(exclusive_scan_i64(hist0g, 256 * ng0 + 1, scan_h0, s));
-  int64_t* h = (int64_t*)pinned(ws, 4 * sizeof(int64_t));
-  if (!h) return CIP_ENOMEM;
-  CIP_HIP_CHECK(hipMemcpyAsync(&h[0], hist0g + 256 * ng0, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipMemcpyAsync(&h[1], err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipMemcpyAsync(&h[2], red + 1, sizeof(double), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  int64_t* h = nullptr;
+  if (const int rc = readback(
+          ws, s, {{hist0g + 256 * ng0, sizeof(int64_t)}, {err, sizeof(unsigned)}, {red + 1, sizeof(double)}}, &h);
+      rc != CIP_OK)
+    return rc;
   const int64_t nruns = h[0];
   std::memcpy(maxabs, &h[2], sizeof(double));
   if (const int rc = plan_error((unsigned)h[1]); rc != CIP_OK) return rc;
@@ -165,11 +164,13 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
     CIP_HIP_CHECK(launch_chunk_counts(tile_vis, ntiles, kOrderWindow, 0, win_off, s));
     CIP_HIP_CHECK(exclusive_scan_i64(win_off, ntiles + 1, scan_tmp, s));
   }
-  int64_t* hl = (int64_t*)pinned(ws, sizeof(int64_t) * (nrange + 2));
-  if (!hl) return CIP_ENOMEM;
-  CIP_HIP_CHECK(hipMemcpyAsync(hl, layer_off, sizeof(int64_t) * (nrange + 1), hipMemcpyDeviceToHost, s));
-  if (order) CIP_HIP_CHECK(hipMemcpyAsync(hl + nrange + 1, win_off + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  int64_t* hl = nullptr;
+  if (const int rc = readback(ws, s,
+                              {{layer_off, sizeof(int64_t) * (nrange + 1)},
+                               {order ? win_off + ntiles : nullptr, sizeof(int64_t)}},
+                              &hl);
+      rc != CIP_OK)
+    return rc;
   pr->plane_chunk_off.assign(hl, hl + nrange + 1);
   const int64_t nwin = order ? hl[nrange + 1] : 0;
   pr->nchunks = pr->plane_chunk_off.back();
@@ -223,15 +224,13 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
   const bool host_fx = nrow == 0 || (rq.do_wstacking && rq.given == nullptr);
   double fxmin = 0.0, fxmax = 0.0;
   if (host_fx) {
-    double* h = (double*)pinned(ws, sizeof(double) * (4 + (size_t)nchan));
-    if (!h) return CIP_ENOMEM;
-    CIP_HIP_CHECK(hipMemcpyAsync(h + 4, fx, sizeof(double) * nchan, hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
-    fxmin = h[4];
-    fxmax = h[4];
+    double* h = nullptr;
+    if (const int rc = readback(ws, s, {{fx, sizeof(double) * nchan}}, &h); rc != CIP_OK) return rc;
+    fxmin = h[0];
+    fxmax = h[0];
     for (int64_t c = 1; c < nchan; ++c) {
-      fxmin = std::fmin(fxmin, h[4 + c]);
-      fxmax = std::fmax(fxmax, h[4 + c]);
+      fxmin = std::fmin(fxmin, h[c]);
+      fxmax = std::fmax(fxmax, h[c]);
     }
     if (!(fxmin > 0.0) || !std::isfinite(fxmax)) return set_error(CIP_EINVAL, "channel frequencies must be positive");
   }
@@ -258,11 +257,9 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
       CIP_HIP_CHECK(hipMemsetAsync(rerr, 0, sizeof(unsigned), s));
       CIP_HIP_CHECK(launch_ragged_lengths(ragged->chan_start, ragged->chan_stop, nrow, nchan, off, rerr, s));
       CIP_HIP_CHECK(exclusive_scan_i64(off, nrow + 1, scan_tmp, s));
-      int64_t* hr = (int64_t*)pinned(ws, 2 * sizeof(int64_t));
-      if (!hr) return CIP_ENOMEM;
-      CIP_HIP_CHECK(hipMemcpyAsync(&hr[0], off + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-      CIP_HIP_CHECK(hipMemcpyAsync(&hr[1], rerr, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-      CIP_HIP_CHECK(hipStreamSynchronize(s));
+      int64_t* hr = nullptr;
+      if (const int rc = readback(ws, s, {{off + nrow, sizeof(int64_t)}, {rerr, sizeof(unsigned)}}, &hr); rc != CIP_OK)
+        return rc;
       if ((unsigned)hr[1] != 0u) return set_error(CIP_EINVAL, "row slice channel range outside [0, nchan)");
       if (hr[0] != ragged->nvis) return set_error(CIP_EINVAL, "visibility count differs from the row slices' total");
       CIP_HIP_CHECK(launch_ragged_expand(off, ragged->chan_start, nrow, delta, seg_row, s));
@@ -295,10 +292,8 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
     const int nb = 256;
     CIP_ALLOC(wpart, double, "w_partial", 2 * nb)
     CIP_HIP_CHECK(launch_w_range(rq.uvw, nrow, fxmin, fxmax, wpart, nb, s));
-    double* hw = (double*)pinned(ws, sizeof(double) * 2 * nb);
-    if (!hw) return CIP_ENOMEM;
-    CIP_HIP_CHECK(hipMemcpyAsync(hw, wpart, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    double* hw = nullptr;
+    if (const int rc = readback(ws, s, {{wpart, sizeof(double) * 2 * nb}}, &hw); rc != CIP_OK) return rc;
     wmin = INFINITY;
     wmax = -INFINITY;
     for (int i = 0; i < nb; ++i) {
@@ -377,11 +372,8 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
     CIP_ALLOC(partial, double, "prep_partial_reuse", 2 * nblk + kPrepFinalScratch)
     CIP_HIP_CHECK(launch_prep_reduce(m, rq.vis, vis_dtype, rq.wgt, wgt_dtype, out->g, err, partial, s));
     CIP_HIP_CHECK(launch_prep_final(partial, nblk, red, s));
-    unsigned* h = (unsigned*)pinned(ws, 4 * sizeof(double));
-    if (!h) return CIP_ENOMEM;
-    CIP_HIP_CHECK(hipMemcpyAsync(h, err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipMemcpyAsync((double*)h + 1, red + 1, sizeof(double), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    unsigned* h = nullptr;
+    if (rc = readback(ws, s, {{err, sizeof(unsigned)}, {red + 1, sizeof(double)}}, &h); rc != CIP_OK) return rc;
     std::memcpy(&maxabs, (double*)h + 1, sizeof(double));
     if (rc = plan_error(h[0]); rc != CIP_OK) return rc;
     out->plan = ws->saved_plan;

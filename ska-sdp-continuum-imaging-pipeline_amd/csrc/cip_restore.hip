@@ -418,29 +418,13 @@ int restore_impl(const double* model, const double* residual, int64_t nx, int64_
   CIP_BEGIN_CALL(hip_stream, false)
   CIP_ALLOC(rows, uint32_t, "restore_rows", ntiles)
   CIP_ALLOC(taps, double, "restore_taps", kMaxTaps)
-  const std::vector<double> key = {bm->a, bm->b, bm->c, (double)R};
-  if (ws->restore_key != key) {
-    ws->restore_key.clear();
-    if (!ws->restore_pinned) {
-      if (hipHostMalloc(&ws->restore_pinned, sizeof(double) * kMaxTaps) != hipSuccess) {
-        ws->restore_pinned = nullptr;
-        return set_error(CIP_ENOMEM, "hipHostMalloc failed");
-      }
-      CIP_HIP_CHECK(hipEventCreateWithFlags(&ws->ev_restore, hipEventDisableTiming));
-    } else {
-      // the last upload has read the staging (it has, unless that stream is far behind)
-      CIP_HIP_CHECK(hipEventSynchronize(ws->ev_restore));
-    }
-    fill_taps(bm, R, (double*)ws->restore_pinned);
-    const size_t bytes = sizeof(double) * (size_t)((2 * R + 1) * (2 * R + 1));
-    CIP_HIP_CHECK(hipMemcpyAsync(taps, ws->restore_pinned, bytes, hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipEventRecord(ws->ev_restore, s));
-    ws->restore_key = key;
-  }
+  const size_t bytes = sizeof(double) * (size_t)((2 * R + 1) * (2 * R + 1));
+  if (const int rc = host_table(ws, "restore_taps", {bm->a, bm->b, bm->c, (double)R}, taps, bytes, s,
+                                [&](void* staging) { fill_taps(bm, R, (double*)staging); });
+      rc != CIP_OK)
+    return rc;
   CIP_HIP_CHECK(launch_restore(model, residual, out, nx, ny, (int)R, taps, rows, s));
-  // the work is only queued: a later call on another stream waits for this one
-  // before it touches the workspace (begin_call)
-  ws->async_stream = s;
+  leave_queued(call);
   return CIP_OK;
 }
 

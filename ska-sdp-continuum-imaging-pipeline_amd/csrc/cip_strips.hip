@@ -347,11 +347,10 @@ int cip_strip_split(const double* uvw, int64_t nrow, const double* freq, int64_t
   CIP_HIP_CHECK(exclusive_scan_i64(row_runs, nrow + 1, scan_tmp, s));
   CIP_HIP_CHECK(exclusive_scan_i64(row_vis, nrow + 1, scan_tmp, s));
   if (!slice_uvw) {
-    int64_t* h = (int64_t*)pinned(ws, 2 * sizeof(int64_t));
-    if (!h) return CIP_ENOMEM;
-    CIP_HIP_CHECK(hipMemcpyAsync(&h[0], row_runs + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipMemcpyAsync(&h[1], row_vis + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t* h = nullptr;
+    if (const int rc = readback(ws, s, {{row_runs + nrow, sizeof(int64_t)}, {row_vis + nrow, sizeof(int64_t)}}, &h);
+        rc != CIP_OK)
+      return rc;
     counts[0] = h[0];
     counts[1] = h[1];
     return CIP_OK;

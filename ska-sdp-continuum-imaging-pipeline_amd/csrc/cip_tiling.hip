@@ -220,10 +220,8 @@ int cip_tile_runs(const double* uvw, int64_t nrow, const double* freq, int64_t n
   CIP_HIP_CHECK(launch_tile_run_count(uvw, nrow, winv, nchan, tile_size3[0], tile_size3[1], tile_size3[2], row_runs,
                                       s));
   CIP_HIP_CHECK(exclusive_scan_i64(row_runs, nrow + 1, tmp, s));
-  int64_t* h = (int64_t*)pinned(ws, sizeof(int64_t));
-  if (!h) return CIP_ENOMEM;
-  CIP_HIP_CHECK(hipMemcpyAsync(h, row_runs + nrow, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  int64_t* h = nullptr;
+  if (const int rc = readback(ws, s, {{row_runs + nrow, sizeof(int64_t)}}, &h); rc != CIP_OK) return rc;
   const int64_t total = h[0];
   if (run_key == nullptr) {
     *n_runs = total;

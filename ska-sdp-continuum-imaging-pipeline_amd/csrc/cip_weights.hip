@@ -125,14 +125,6 @@ __device__ __forceinline__ void store_group(OutT* p, int k0, int n, bool vec, co
     if (k0 + j < n) p[k0 + j] = (OutT)r[j];
 }
 
-// the wave's sum in lane 0, in a fixed order
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // lane t: row t / nseg, channels [kWeightSeg (t % nseg), ...) of it.
 // counts: samples added, samples with w > 0 outside, bad samples
 template <int WK>
@@ -478,14 +470,14 @@ int make_walk(Workspace* ws, hipStream_t s, const double* uvw, int64_t nrow, con
   return CIP_OK;
 }
 
-// host: pinned staging of >= 3 words. Waits for the stream once.
-int density_run(Workspace* ws, hipStream_t s, const char* who, const WeightWalk& a, int64_t* density, int64_t* host,
+// Waits for the stream once.
+int density_run(Workspace* ws, hipStream_t s, const char* who, const WeightWalk& a, int64_t* density,
                 int64_t* counts_out) {
   CIP_ALLOC(counts, unsigned long long, "weight_counts", 3)
   CIP_HIP_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), s));
   CIP_HIP_CHECK(launch_weight_density(a, density, counts, s));
-  CIP_HIP_CHECK(hipMemcpyAsync(host, counts, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  int64_t* host = nullptr;
+  if (const int rc = readback(ws, s, {{counts, 3 * sizeof(int64_t)}}, &host); rc != CIP_OK) return rc;
   if (counts_out)
     for (int k = 0; k < 3; ++k) counts_out[k] = host[k];
   if (host[2] > 0)
@@ -494,14 +486,12 @@ int density_run(Workspace* ws, hipStream_t s, const char* who, const WeightWalk&
   return CIP_OK;
 }
 
-// host: pinned staging of >= sizeof(WeightStatPart). stats: sum_w, sum_d2, non-zero cells
-int stats_run(Workspace* ws, hipStream_t s, const int64_t* density, const cip_weight_grid& gr, void* host,
-              double* stats) {
+// stats: sum_w, sum_d2, non-zero cells. Waits for the stream once.
+int stats_run(Workspace* ws, hipStream_t s, const int64_t* density, const cip_weight_grid& gr, double* stats) {
   CIP_ALLOC(part, WeightStatPart, "weight_stat_part", kStatBlocks + 1)
   CIP_HIP_CHECK(launch_weight_stats(density, grid_cells(gr), gr.quantum, part, s));
-  CIP_HIP_CHECK(hipMemcpyAsync(host, part + kStatBlocks, sizeof(WeightStatPart), hipMemcpyDeviceToHost, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
-  const WeightStatPart* p = (const WeightStatPart*)host;
+  const WeightStatPart* p = nullptr;
+  if (const int rc = readback(ws, s, {{part + kStatBlocks, sizeof(WeightStatPart)}}, &p); rc != CIP_OK) return rc;
   stats[0] = (double)p->sum * gr.quantum;
   stats[1] = p->d2;
   stats[2] = (double)p->nz;
@@ -523,8 +513,6 @@ int apply_check(const char* who, int mode, double f2, const void* out, int out_d
   return CIP_OK;
 }
 
-constexpr size_t kWeightStaging = 64;  // bytes of pinned staging an entry point takes
-
 int weight_density_impl(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const void* wgt,
                         int wgt_dtype, const cip_weight_grid* gr, void* hip_stream, int64_t* density,
                         int64_t* counts_out) {
@@ -535,20 +523,16 @@ int weight_density_impl(const double* uvw, int64_t nrow, const double* freq, int
   if (nrow == 0) return CIP_OK;
   if (!density) return set_error(CIP_EINVAL, "cip_weight_density: density_io must not be NULL");
   CIP_BEGIN_CALL(hip_stream, false)
-  int64_t* host = (int64_t*)pinned(ws, kWeightStaging);
-  if (!host) return CIP_ENOMEM;
   WeightWalk a;
   if (const int rc = make_walk(ws, s, uvw, nrow, freq, nchan, wgt, wgt_dtype, *gr, &a); rc != CIP_OK) return rc;
-  return density_run(ws, s, who, a, density, host, counts_out);
+  return density_run(ws, s, who, a, density, counts_out);
 }
 
 int weight_stats_impl(const int64_t* density, const cip_weight_grid* gr, void* hip_stream, double* stats_out) {
   if (const int rc = grid_check("cip_weight_stats", gr); rc != CIP_OK) return rc;
   if (!density || !stats_out) return set_error(CIP_EINVAL, "cip_weight_stats: density and stats_out must not be NULL");
   CIP_BEGIN_CALL(hip_stream, false)
-  void* host = pinned(ws, kWeightStaging);
-  if (!host) return CIP_ENOMEM;
-  return stats_run(ws, s, density, *gr, host, stats_out);
+  return stats_run(ws, s, density, *gr, stats_out);
 }
 
 int weight_apply_impl(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const void* wgt,
@@ -583,15 +567,13 @@ int imaging_weights_impl(const double* uvw, int64_t nrow, const double* freq, in
   if (info_out) *info_out = info;
   if (nrow == 0) return CIP_OK;
   CIP_BEGIN_CALL(hip_stream, false)
-  int64_t* host = (int64_t*)pinned(ws, kWeightStaging);
-  if (!host) return CIP_ENOMEM;
   const int64_t nvis = nrow * nchan;
   double wmax = 1.0;
   if (wgt) {
     CIP_ALLOC(mx, unsigned long long, "weight_max", 2)
     CIP_HIP_CHECK(launch_weight_max(wgt, wgt_dtype, nvis, mx, s));
-    CIP_HIP_CHECK(hipMemcpyAsync(host, mx, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t* host = nullptr;
+    if (const int rc = readback(ws, s, {{mx, 2 * sizeof(int64_t)}}, &host); rc != CIP_OK) return rc;
     if (host[1] > 0)
       return set_error(CIP_ERANGE, "cip_imaging_weights: " + std::to_string(host[1]) + " weights are negative or NaN");
     std::memcpy(&wmax, &host[0], sizeof(double));
@@ -608,9 +590,9 @@ int imaging_weights_impl(const double* uvw, int64_t nrow, const double* freq, in
   WeightWalk a;
   if (const int rc = make_walk(ws, s, uvw, nrow, freq, nchan, wgt, wgt_dtype, gr, &a); rc != CIP_OK) return rc;
   int64_t counts[3];
-  if (const int rc = density_run(ws, s, who, a, density, host, counts); rc != CIP_OK) return rc;
+  if (const int rc = density_run(ws, s, who, a, density, counts); rc != CIP_OK) return rc;
   double stats[3];
-  if (const int rc = stats_run(ws, s, density, gr, host, stats); rc != CIP_OK) return rc;
+  if (const int rc = stats_run(ws, s, density, gr, stats); rc != CIP_OK) return rc;
   double f2 = 0.0;
   if (mode == CIP_WEIGHT_BRIGGS && stats[0] > 0.0) {
     const double t = 5.0 * std::pow(10.0, -robust);

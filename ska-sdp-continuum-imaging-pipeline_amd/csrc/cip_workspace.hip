@@ -1,7 +1,7 @@
 // cip_workspace.hip - per-thread state of the host API: the error string, the
-// profiler, the (device, thread) workspace with its buffers, FFT plans and
-// side stream, and the call scope every entry point opens.
-#include <algorithm>
+// profiler, the (device, thread) workspace with its buffers, cached host
+// tables, readback staging, FFT plans and side stream, and the call scope
+// every entry point opens.
 #include <cmath>
 #include <mutex>
 #include <thread>
@@ -80,10 +80,10 @@ static void destroy_workspace(Workspace* ws) {
     if (kv.second.ptr) (void)hipFree(kv.second.ptr);
   for (auto& p : ws->plans) (void)hipfftDestroy(p.h);
   if (ws->pinned) (void)hipHostFree(ws->pinned);
-  if (ws->restore_pinned) (void)hipHostFree(ws->restore_pinned);
-  if (ws->ev_restore) (void)hipEventDestroy(ws->ev_restore);
-  if (ws->ms_pinned) (void)hipHostFree(ws->ms_pinned);
-  if (ws->ev_ms) (void)hipEventDestroy(ws->ev_ms);
+  for (auto& kv : ws->tables) {
+    if (kv.second.staging) (void)hipHostFree(kv.second.staging);
+    if (kv.second.uploaded) (void)hipEventDestroy(kv.second.uploaded);
+  }
   if (ws->side) {
     (void)hipStreamSynchronize(ws->side);
     (void)hipStreamDestroy(ws->side);
@@ -164,18 +164,63 @@ void* buf_bytes(Workspace* ws, const char* name, size_t bytes) {
   return b.ptr;
 }
 
-void* pinned(Workspace* ws, size_t bytes) {
-  if (ws->pinned_bytes < bytes) {
-    if (ws->pinned) (void)hipHostFree(ws->pinned);
-    ws->pinned = nullptr;
-    ws->pinned_bytes = 0;
-    if (hipHostMalloc(&ws->pinned, bytes) != hipSuccess) {
+// grow-only pinned host memory (the readback staging and each table's own)
+static void* pinned_grow(void** p, size_t* have, size_t bytes) {
+  if (*have < bytes) {
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipHostMalloc(p, bytes) != hipSuccess) {
+      *p = nullptr;
       set_error(CIP_ENOMEM, "hipHostMalloc failed");
       return nullptr;
     }
-    ws->pinned_bytes = bytes;
+    *have = bytes;
   }
-  return ws->pinned;
+  return *p;
+}
+
+void* pinned(Workspace* ws, size_t bytes) { return pinned_grow(&ws->pinned, &ws->pinned_bytes, bytes); }
+
+int readback_bytes(Workspace* ws, hipStream_t s, std::initializer_list<DevSrc> src, void** host) {
+  const auto slot = [](size_t bytes) { return (bytes + 7) & ~(size_t)7; };
+  size_t total = 0;
+  for (const DevSrc& c : src) total += slot(c.bytes);
+  char* h = (char*)pinned(ws, total);
+  if (!h) return CIP_ENOMEM;
+  size_t at = 0;
+  for (const DevSrc& c : src) {
+    if (c.dev) CIP_HIP_CHECK(hipMemcpyAsync(h + at, c.dev, c.bytes, hipMemcpyDeviceToHost, s));
+    at += slot(c.bytes);
+  }
+  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  *host = h;
+  return CIP_OK;
+}
+
+int host_table_open(Workspace* ws, const char* name, const std::vector<double>& key, size_t bytes, void** staging) {
+  HostTable& t = ws->tables[name];
+  *staging = nullptr;
+  if (t.key == key) return CIP_OK;
+  t.key.clear();
+  if (!t.uploaded) {
+    CIP_HIP_CHECK(hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming));
+  } else {
+    // the last upload has read the staging (it has, unless that stream is far behind)
+    CIP_HIP_CHECK(hipEventSynchronize(t.uploaded));
+  }
+  if (!pinned_grow(&t.staging, &t.staging_bytes, bytes)) return CIP_ENOMEM;
+  *staging = t.staging;
+  return CIP_OK;
+}
+
+int host_table_upload(Workspace* ws, const char* name, const std::vector<double>& key, void* dev, size_t bytes,
+                      hipStream_t s) {
+  HostTable& t = ws->tables[name];
+  CIP_HIP_CHECK(hipMemcpyAsync(dev, t.staging, bytes, hipMemcpyHostToDevice, s));
+  CIP_HIP_CHECK(hipEventRecord(t.uploaded, s));
+  t.key = key;
+  return CIP_OK;
 }
 
 int fft_plan(Workspace* ws, int64_t nu, int64_t nv, hipStream_t s, hipfftHandle* out) {
@@ -199,20 +244,16 @@ int fft_twiddles(Workspace* ws, int64_t n, hipStream_t s, double** out) {
   const std::string name = "fft_twiddle_" + std::to_string(n);
   double* tw = buf<double>(ws, name.c_str(), 2 * n);
   if (!tw) return CIP_ENOMEM;
-  if (std::find(ws->tw_ready.begin(), ws->tw_ready.end(), n) == ws->tw_ready.end()) {
-    std::vector<double> h(2 * n);
+  *out = tw;
+  return host_table(ws, name.c_str(), {(double)n}, tw, sizeof(double) * 2 * n, s, [n](void* staging) {
+    double* h = (double*)staging;
     for (int64_t m = 0; m < n; ++m) {
       // long double arguments: each entry correctly rounded (to within an ulp)
       const long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)n;
       h[2 * m] = (double)cosl(a);
       h[2 * m + 1] = (double)sinl(a);
     }
-    CIP_HIP_CHECK(hipMemcpyAsync(tw, h.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
-    ws->tw_ready.push_back(n);
-  }
-  *out = tw;
-  return CIP_OK;
+  });
 }
 
 int begin_call(void* hip_stream, bool profiled, Call* c) {
@@ -235,6 +276,8 @@ int end_call(const Call& c) {
   if (c.profiled) g_prof.finish();
   return CIP_OK;
 }
+
+void leave_queued(const Call& c) { c.ws->async_stream = c.s; }
 
 }  // namespace cip
 
