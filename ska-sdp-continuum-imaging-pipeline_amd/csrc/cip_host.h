@@ -1,13 +1,16 @@
 // cip_host.h - what the host-side units of libcip_hip.so share (cip_workspace,
 // cip_params, cip_planner, cip_invert, cip_predict and the entry points kept
 // beside their launchers in cip_clean, cip_strips, cip_tiling): the per-thread
-// workspace with its cached host tables (host_table) and its one readback
-// (readback), the planner's request and result, the call scope and the CIP_*
-// switches. Host only and not part of the C ABI (include/cip.h is); units
-// that hold nothing but kernels and launchers include cip_internal.h alone.
+// workspace with its cached host tables (host_table), its one readback
+// (readback), the grid's known-zero state (GridZero) and the plan pipeline
+// (PlanPipeline, PlanScope), the planner's request and result, the call scope
+// that closes itself (Call) and the CIP_* switches. Host only and not part of
+// the C ABI (include/cip.h is); units that hold nothing but kernels and
+// launchers include cip_internal.h alone.
 #pragma once
 #include <hipfft/hipfft.h>
 
+#include <algorithm>
 #include <initializer_list>
 #include <map>
 #include <string>
@@ -104,6 +107,56 @@ struct HostTable {
   hipEvent_t uploaded = nullptr;  // behind the last upload: the next one waits for it before it refills the staging
 };
 
+// The "grid" buffer's known-zero prefix (the masked FFT pass A zeroes what the
+// scatter wrote). A byte count, not a plane count: a call on a smaller grid
+// keeps only its own planes' bytes clean, and a larger one must not trust more.
+struct GridZero {
+  const void* grid_clean = nullptr;  // the buffer, or NULL: nothing is known
+  size_t grid_clean_bytes = 0;       // how many of its leading bytes are zero
+  size_t prefix(const void* p) const { return p == grid_clean ? grid_clean_bytes : 0; }
+  bool covers(const void* p, size_t n) const { return p && prefix(p) >= n; }  // the first n bytes of p count as zero
+  void mark(const void* p, size_t n) { *this = {p, std::max(prefix(p), n)}; }  // a larger prefix of the buffer stays
+  void invalidate() { *this = GridZero(); }  // also when the buffer is reallocated (grid_buffer)
+};
+
+// CIP_ASYNC | CIP_PIPELINE (cip_ms2dirty): consecutive calls alternate between
+// two sets of planner buffers (parity; buf() appends it to buffer names while
+// a PlanScope plans), so the planner of call k + 1 runs on a plan stream
+// beside call k's scatter and FFT; it only waits for call k - 1's work on the
+// caller's stream (ev_done[parity]: its scatter read the plan, its FFT the
+// masks and weight sum). One plan stream per parity. Only these methods and
+// PlanScope (cip_workspace.hip) touch the fields.
+struct PlanPipeline {
+  hipStream_t plan_stream = nullptr, plan_stream1 = nullptr;
+  hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_planned = nullptr, ev_entry = nullptr;
+  int parity = 0;
+  bool parity_scope = false;
+  bool plan_unscoped = false;  // a planner used the parity-0 names on a caller's stream since the last pipelined call
+
+  bool odd_names() const { return parity_scope && parity; }  // buf_bytes: names carry "~1"
+  void planner_starts() { plan_unscoped = plan_unscoped || !parity_scope; }  // prepare()
+  void rewind() { parity = 0; }  // cip_dirty2ms plans into the parity-0 buffers and leaves the next invert there
+  void destroy();                // drains and destroys the streams and events
+};
+
+// One invert's hold on the pipeline, in the order every return path keeps:
+// open -> the planner on ps, buf() names carrying the parity -> join (plain
+// names again; s waits for ev_planned, once, also after a failed plan) ->
+// ~PlanScope (joins if nobody did, then records ev_done[parity] on s, behind
+// everything the call queued there: the next planner of this parity waits for
+// it). A call that is not pipelined plans on s: all of it no-ops.
+struct PlanScope {
+  PlanPipeline& pl;
+  const hipStream_t s;
+  hipStream_t ps = s;  // where the planner runs
+  bool armed = false, joined = true;
+  // pipelined: streams and events on first use, the plan streams wait for s if
+  // plan_unscoped, the parity flips, ps waits for ev_done[parity]; else parity 0
+  int open(bool pipelined);
+  int join();
+  ~PlanScope();
+};
+
 struct Workspace {
   int device = 0;  // the device every buffer, stream and event belongs to
   std::map<std::string, DevBuf> bufs;
@@ -114,31 +167,10 @@ struct Workspace {
   // second stream: zeroes the first grid plane while the planner runs
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool side_pending = false;
-  // the "grid" buffer when it is known all-zero (the masked FFT pass A zeroes
-  // what the scatter wrote), else NULL
-  double* grid_clean = nullptr;
-  // how many of its leading BYTES are known zero: a call on a smaller grid
-  // zeroes (and keeps clean) only its own planes' bytes, so the state is a byte
-  // count, not a plane count (a later larger-geometry call must not trust it)
-  size_t grid_clean_bytes = 0;
-  // CIP_ASYNC pipelining (cip_ms2dirty): consecutive calls alternate between
-  // two sets of planner buffers (parity; buf() appends the parity to buffer
-  // names while parity_scope is set), so the planner of call k + 1 runs on
-  // plan_stream beside call k's scatter and FFT; it only waits for
-  // call k - 1's work on the caller's stream (ev_done[parity]: its scatter
-  // read the plan, its FFT the masks and weight sum); the caller's stream
-  // waits for the plan (ev_planned). One plan stream per parity.
-  hipStream_t plan_stream = nullptr, plan_stream1 = nullptr;
-  hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_planned = nullptr, ev_entry = nullptr;
-  uint64_t call_seq = 0;
-  int parity = 0;
-  bool parity_scope = false;
-  // a planner ran on a caller's stream (parity-0 buffer names) since the last
-  // pipelined call: the next pipelined planner waits for that stream
-  bool plan_unscoped = false;
-  // the stream of the last call that left its work queued (leave_queued): a
-  // call on another stream first waits for it (the workspace is shared)
+  GridZero grid_zero;
+  PlanPipeline pipeline;
+  // the last call left work queued on async_stream (~Call): a call on another stream first waits for it
+  bool async_queued = false;
   hipStream_t async_stream = nullptr;
   // the last complete plan (its buffers stay untouched until the next planner
   // runs) and the geometry it was made for: CIP_REUSE_PLAN calls with the
@@ -158,6 +190,8 @@ template <typename T>
 T* buf(Workspace* ws, const char* name, int64_t count) {
   return (T*)buf_bytes(ws, name, (size_t)(count > 0 ? count : 1) * sizeof(T));
 }
+// the uv grid ("grid", never parity-named); growing it invalidates grid_zero
+double* grid_buffer(Workspace* ws, size_t bytes);
 #define CIP_ALLOC(var, T, name, n)  \
   T* var = buf<T>(ws, name, (n));   \
   if (!var) return CIP_ENOMEM;
@@ -202,23 +236,27 @@ int zero_on_side(Workspace* ws, void* p, size_t bytes, hipStream_t s);
 int join_side(Workspace* ws, hipStream_t s);
 
 // One entry-point call: its workspace and stream, and (profiled calls) the
-// event that starts span 5, the whole call.
+// event that starts span 5, the whole call. The scope closes itself: unless
+// end_call waited for the stream, ~Call notes it in the workspace on every
+// return path, so a later call on another stream waits for it in begin_call.
 struct Call {
   Workspace* ws = nullptr;
   hipStream_t s = nullptr;
   bool profiled = false;
   hipEvent_t t0 = nullptr;
+  bool synced = false;  // end_call waited for s: nothing of this call is queued
+  Call() = default;
+  Call(const Call&) = delete;
+  Call& operator=(const Call&) = delete;
+  ~Call();
 };
-// Clears the thread's error, takes its workspace (which counts the call and
-// arms the reaper, so argument checks come first), waits for an earlier
-// CIP_ASYNC call on another stream; profiled: resets the profiler and marks
-// the start.
+// Clears the thread's error, takes its workspace (which arms the reaper, so
+// argument checks come first), waits for an earlier call's work queued on
+// another stream; profiled: resets the profiler and marks the start.
 int begin_call(void* hip_stream, bool profiled, Call* c);
-// Closes span 5 (profiled calls), synchronises the stream, reads the profile.
-int end_call(const Call& c);
-// Instead of end_call: the call's work is only queued, so a later call on
-// another stream waits for this one before it touches the workspace (begin_call)
-void leave_queued(const Call& c);
+// Closes span 5; wait (or a profile to read): synchronises the stream and reads
+// the profile; else the work stays queued (CIP_ASYNC) and ~Call notes the stream.
+int end_call(Call& c, bool wait = true);
 // the usual opening of an entry point, after its argument checks: declares
 // `call`, and `ws` and `s` as the bodies (and CIP_ALLOC) name them
 #define CIP_BEGIN_CALL(hip_stream, profiled)                                              \
@@ -302,19 +340,52 @@ struct PlanRequest {
   bool want_group = true;  // w-plane groups (wstack_group); false: one plane per work unit
   bool wide_tile = false;  // a cip_ms2dirty* call: the plan may use a larger work tile (scatter_tile_shape)
   int64_t plane_begin = 0, plane_end = -1;
-};
-// cip_planner.hip. grid_out (may be NULL): also takes the workspace grid and
-// zeroes its first plane group on the side stream (the caller joins it)
-int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, double** grid_out = nullptr);
 
-// Correction vectors, FFT plan / twiddles and the pass-A buffer for one
-// (grid, image) geometry (cip_invert.hip dirty_stage)
-struct DirtyStage {
-  int64_t npix_x = 0, npix_y = 0;
-  double px = 0, py = 0;
-  bool fast = false;
-  hipfftHandle plan = nullptr;
-  double *tw_u = nullptr, *tw_v = nullptr, *fft_h = nullptr, *cx = nullptr, *cy = nullptr;
+  // What to plan for: an image and an accuracy,
+  static PlanRequest image(int64_t npix_x, int64_t npix_y, double px, double py, double epsilon, int support) {
+    PlanRequest rq;
+    rq.npix_x = npix_x, rq.npix_y = npix_y, rq.px = px, rq.py = py, rq.epsilon = epsilon, rq.support = support;
+    return rq;
+  }
+  // or given parameters (NULL: the caller reports it) and the call's flags. A dummy image size: the planner
+  // then consults it for nothing but its CIP_REUSE_PLAN key, which a call with given parameters never matches.
+  static PlanRequest fixed(const cip_gridder_params* params, double px, double py, int flags) {
+    PlanRequest rq = image(2, 2, px, py, 0.0, params ? params->support : 0);
+    rq.do_wstacking = params ? params->do_wstacking : 0;
+    rq.packed = (flags & CIP_ACC_SINGLE) != 0;
+    rq.given = params;
+    return rq;
+  }
+  // of dense rows (ragged row slices: the caller then sets `ragged`),
+  PlanRequest& dense(const double* uvw_, int64_t nrow_, const double* freq_, int64_t nchan_, const void* vis_,
+                     int vis_dtype_, const void* wgt_, int wgt_dtype_) {
+    uvw = uvw_, nrow = nrow_, freq = freq_, nchan = nchan_;
+    vis = vis_, vis_dtype = vis_dtype_, wgt = wgt_, wgt_dtype = wgt_dtype_;
+    return *this;
+  }
+  // raw linear-feed rows (CIP_POL4I),
+  PlanRequest& raw(const double* uvw_, int64_t nrow_, const double* freq_, int64_t nchan_, const void* vis4,
+                   const uint8_t* flags4_, const float* wgt4) {
+    flags4 = flags4_;
+    return dense(uvw_, nrow_, freq_, nchan_, vis4, CIP_POL4I, wgt4, CIP_POL4I);
+  }
 };
+
+// prepare()'s decision about the workspace grid: an invert's first plane group.
+// The packed class grids into complex64 planes on the pruned-FFT path (half
+// the flush and pass-A bytes); CIP_GRID_F32=0 keeps complex128 (A/B)
+inline bool grid_planes_f32(bool packed, const GridGeometry& g, int64_t npix_x, int64_t npix_y) {
+  return packed && grid_is_transposed(g, npix_x, npix_y) && grid_f32_enabled();
+}
+struct GridUse {
+  bool beside = false;  // in: the planner runs on the call's stream, so zero the group beside it (zero_on_side)
+  double* grid = nullptr;
+  size_t bytes = 0;      // of the group's planes in their cell type
+  bool f32 = false;      // complex64 planes (grid_planes_f32)
+  bool zeroed = false;   // the bytes count as zero: left clean by the last invert, or the side memset
+  bool pending = false;  // the side memset is queued: the caller joins it (join_side) whatever happens
+};
+// cip_planner.hip. grid_out (may be NULL): also takes the workspace grid
+int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, GridUse* grid_out = nullptr);
 
 }  // namespace cip

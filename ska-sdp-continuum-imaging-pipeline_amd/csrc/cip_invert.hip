@@ -64,42 +64,44 @@ static int scatter_plane(const Prepared& pp, const PlanRequest& rq, int64_t q, c
 // Correction vectors, FFT plan / twiddles and the pass-A buffer for one
 // (grid, image) geometry; then per plane: FFT + crop/correct (2-D) or the
 // w-screen accumulation, and the final w-stacking correction.
+struct DirtyStage {
+  int64_t npix_x = 0, npix_y = 0;
+  double px = 0, py = 0;
+  bool fast = false;
+  hipfftHandle plan = nullptr;
+  double *tw_u = nullptr, *tw_v = nullptr, *fft_h = nullptr, *cx = nullptr, *cy = nullptr;
+};
 static int dirty_stage(Workspace* ws, const GridGeometry& g, int64_t npix_x, int64_t npix_y, double px, double py,
                        hipStream_t s, DirtyStage* st) {
-  st->npix_x = npix_x;
-  st->npix_y = npix_y;
-  st->px = px;
-  st->py = py;
+  *st = DirtyStage{npix_x, npix_y, px, py};
   if (const int rc = correction_vectors(ws, g, npix_x, npix_y, s, &st->cx, &st->cy); rc != CIP_OK) return rc;
   // pruned FFT (cip_fft.hip) for power-of-two grids; hipFFT 2-D otherwise
   // (CIP_FFT_PRUNED=0 forces the latter)
   st->fast = grid_is_transposed(g, npix_x, npix_y);
-  if (st->fast) {
-    int rc = fft_twiddles(ws, g.nu, s, &st->tw_u);
-    if (rc != CIP_OK) return rc;
-    rc = fft_twiddles(ws, g.nv, s, &st->tw_v);
-    if (rc != CIP_OK) return rc;
-    st->fft_h = buf<double>(ws, "fft_pass_a", 2 * npix_x * g.nv);
-    if (!st->fft_h) return CIP_ENOMEM;
-  } else {
-    const int rc = fft_plan(ws, g.nu, g.nv, s, &st->plan);
-    if (rc != CIP_OK) return rc;
-  }
-  return CIP_OK;
+  if (!st->fast) return fft_plan(ws, g.nu, g.nv, s, &st->plan);
+  if (const int rc = fft_twiddles(ws, g.nu, s, &st->tw_u); rc != CIP_OK) return rc;
+  if (const int rc = fft_twiddles(ws, g.nv, s, &st->tw_v); rc != CIP_OK) return rc;
+  st->fft_h = buf<double>(ws, "fft_pass_a", 2 * npix_x * g.nv);
+  return st->fft_h ? CIP_OK : CIP_ENOMEM;
 }
 
 // plane p's grid (consumed: the hipFFT path transforms it in place) into
-// dirty_out (overwritten for p == 0, accumulated after it)
-// dmask (pruned FFT only, may be NULL): the grid tiles the scatter wrote; the
-// rest of the grid is zero, and pass A zeroes the masked tiles after reading
-// norm (pruned 2-D path only, may be NULL): device weight sum the image is
-// divided by in pass B's epilogue (CIP_NORMALISE)
-// rowbits (with dmask): the plane's tile-row bits (row_bits_kernel)
-// acc_f32: dirty_out is the packed class's float plane accumulator
+// dirty_out (overwritten by the first plane, accumulated after it)
+struct PlaneExtras {
+  // (pruned FFT only, may be NULL): the grid tiles the scatter wrote; the rest
+  // of the grid is zero, and pass A zeroes the masked tiles after reading
+  const uint32_t* dmask = nullptr;
+  // (pruned 2-D path only, may be NULL): device weight sum the image is
+  // divided by in pass B's epilogue (CIP_NORMALISE)
+  const double* norm = nullptr;
+  const uint32_t* rowbits = nullptr;  // (with dmask): the plane's tile-row bits (row_bits_kernel)
+  int first = -1;                     // overwrite the image (1) or add to it (0); -1: plane 0 overwrites
+  bool acc_f32 = false;               // dirty_out is the packed class's float plane accumulator
+};
 static int plane_to_dirty(const DirtyStage& st, const GridGeometry& g, int64_t p, double* grid, double* dirty_out,
-                          hipStream_t s, const uint32_t* dmask = nullptr, const double* norm = nullptr,
-                          const uint32_t* rowbits = nullptr, int first = -1, bool acc_f32 = false) {
-  if (first < 0) first = p == 0;  // the first plane overwrites the image, later ones add
+                          hipStream_t s, const PlaneExtras& x = PlaneExtras()) {
+  const uint32_t *dmask = x.dmask, *rowbits = x.rowbits;
+  const int first = x.first < 0 ? p == 0 : x.first;
   hipEvent_t f0 = g_prof.mark(s);
   // 16384-point fp64 columns of a 2-D image: pass B by even / odd halves
   // (cip_fft.hip fft_cols_eo_kernel), pass A writing H in that order
@@ -116,17 +118,15 @@ static int plane_to_dirty(const DirtyStage& st, const GridGeometry& g, int64_t p
   // pass B carries the crop epilogue: it is booked under "fft"
   if (st.fast)
     CIP_HIP_CHECK(launch_fft_cols(st.fft_h, g.nv, st.npix_x, st.npix_y, st.tw_v, g.do_wstacking ? 1 : 0, dirty_out,
-                                  st.cx, st.cy, st.px, st.py, w_plane, first, g.do_wstacking ? nullptr : norm,
-                                  dmask ? rowbits : nullptr, g.grid_f32 != 0, acc_f32, eo, s));
+                                  st.cx, st.cy, st.px, st.py, w_plane, first, g.do_wstacking ? nullptr : x.norm,
+                                  dmask ? rowbits : nullptr, g.grid_f32 != 0, x.acc_f32, eo, s));
   hipEvent_t f1 = g_prof.mark(s);
   g_prof.span(3, f0, f1);
-  if (st.fast) {
-  } else if (g.do_wstacking) {
+  if (!st.fast && g.do_wstacking)
     CIP_HIP_CHECK(launch_wplane_accumulate(grid, g, st.npix_x, st.npix_y, st.px, st.py, w_plane, first, dirty_out,
                                            s));
-  } else {
+  else if (!st.fast)
     CIP_HIP_CHECK(launch_crop_correct_2d(grid, g, st.npix_x, st.npix_y, st.cx, st.cy, dirty_out, s));
-  }
   g_prof.span(4, f1, g_prof.mark(s));
   return CIP_OK;
 }
@@ -144,12 +144,22 @@ static int finish_dirty(Workspace* ws, const DirtyStage& st, const cip_gridder_p
   return CIP_OK;
 }
 
+// CIP_PSF: unit visibilities (vis is not read); then the rows' NULL-pointer check
+static int psf_and_inputs(PlanRequest* rq, int flags) {
+  if (flags & CIP_PSF) {
+    rq->vis = nullptr;
+    if (rq->vis_dtype != CIP_POL4I) rq->vis_dtype = CIP_C64;
+  }
+  if (rq->nrow > 0 && (!rq->uvw || !rq->freq || (!rq->vis && !(flags & CIP_PSF))))
+    return set_error(CIP_EINVAL, "NULL input pointer");
+  return CIP_OK;
+}
+
 // Grid visibilities (dense MS rows, or ragged row slices) onto nplanes
 // resident accumulator planes (no zeroing: += onto what they hold), and add
 // their weight sum to *sum_wgt.
-// rq: the visibilities (dense rows, or rq.ragged), the fixed parameters
-// (rq.given) and the pixel sizes, as the entry point received them; the
-// planner's remaining fields are filled here. t: where they go.
+// rq: the visibilities (dense rows, or rq.ragged) and the fixed parameters
+// (PlanRequest::fixed). t: where they go.
 struct GridTarget {
   int64_t npix_x = 0, npix_y = 0;  // the image: decides the grid's HBM layout
   int flags = 0;
@@ -160,30 +170,16 @@ struct GridTarget {
   uint32_t* strip_bits = nullptr;  // cip_grid_tiles_strip_mask's tile_bits
 };
 static int grid_accumulate(PlanRequest rq, const GridTarget& t, void* hip_stream) {
-  const cip_gridder_params* params = rq.given;
   int flags = t.flags;
   double* const grids = t.grids;
   const int64_t row0 = t.row0, nrows = t.nrows;
   if (flags & ~(CIP_ACC_SINGLE | CIP_PSF | CIP_GRID_ZEROED)) return set_error(CIP_EINVAL, "unknown flags");
-  if (!params || !grids) return set_error(CIP_EINVAL, "NULL params or grids");
+  if (!rq.given || !grids) return set_error(CIP_EINVAL, "NULL params or grids");
   // the flush's private-cell stores (CIP_GRID_ZEROED) write 16-byte cells:
   // planes that are only 8-byte aligned take the atomic path instead
   if (((uintptr_t)grids & 15u) != 0u) flags &= ~CIP_GRID_ZEROED;
-  if (flags & CIP_PSF) {
-    rq.vis = nullptr;
-    if (rq.vis_dtype != CIP_POL4I) rq.vis_dtype = CIP_C64;
-  }
-  if (rq.nrow > 0 && (!rq.uvw || !rq.freq || (!rq.vis && !(flags & CIP_PSF))))
-    return set_error(CIP_EINVAL, "NULL input pointer");
+  if (const int rc = psf_and_inputs(&rq, flags); rc != CIP_OK) return rc;
   CIP_BEGIN_CALL(hip_stream, true)
-  // a dummy image size: with given parameters the planner consults it for
-  // nothing but its CIP_REUSE_PLAN key, which a call with given parameters
-  // never matches
-  rq.npix_x = rq.npix_y = 2;
-  rq.epsilon = 0.0;
-  rq.support = params->support;
-  rq.do_wstacking = params->do_wstacking;
-  rq.packed = (flags & CIP_ACC_SINGLE) != 0;
   Prepared pp;
   int rc = prepare(ws, rq, s, &pp);
   if (rc != CIP_OK) return rc;
@@ -220,8 +216,7 @@ static int grid_accumulate(PlanRequest rq, const GridTarget& t, void* hip_stream
   mode.zeroed = true;  // no zeroing: += onto what the planes hold
   mode.accumulate = (flags & CIP_GRID_ZEROED) == 0;
   for (int64_t q = 0; q * G < g.nplanes; ++q) {
-    rc = scatter_plane(pp, rq, q, mode, grids + q * G * plane_elems, s);
-    if (rc != CIP_OK) return rc;
+    if (rc = scatter_plane(pp, rq, q, mode, grids + q * G * plane_elems, s); rc != CIP_OK) return rc;
   }
   if (t.sum_wgt) CIP_HIP_CHECK(launch_add_scalar(pp.red, t.sum_wgt, s));
   if (t.strip_bits) CIP_HIP_CHECK(launch_strip_mask(wmask, g, row0, g.support - 1, t.strip_bits, s));
@@ -255,115 +250,39 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
     return set_error(CIP_EINVAL, "CIP_REUSE_PLAN cannot be combined with CIP_PIPELINE");
   rq.do_wstacking = (flags & CIP_WSTACKING) ? 1 : 0;
   const bool normalise = (flags & CIP_NORMALISE) != 0;
-  const bool packed = rq.packed = (flags & CIP_ACC_SINGLE) != 0;
+  rq.packed = (flags & CIP_ACC_SINGLE) != 0;
   rq.reuse = (flags & CIP_REUSE_PLAN) != 0;
   rq.wide_tile = true;
-  if (flags & CIP_PSF) {
-    rq.vis = nullptr;
-    if (rq.vis_dtype != CIP_POL4I) rq.vis_dtype = CIP_C64;
-  }
   if (!dirty_out) return set_error(CIP_EINVAL, "dirty_out is NULL");
-  if (rq.nrow > 0 && (!rq.uvw || !rq.freq || (!rq.vis && !(flags & CIP_PSF))))
-    return set_error(CIP_EINVAL, "NULL input pointer");
+  if (const int rc = psf_and_inputs(&rq, flags); rc != CIP_OK) return rc;
   CIP_BEGIN_CALL(hip_stream, true)
-  // CIP_ASYNC | CIP_PIPELINE (resident inputs): the planner on the
-  // workspace's plan stream with this call's parity of planner buffers, after
-  // the last scatter of the call before the previous one (the last user of
-  // those buffers) - it then runs beside the previous call's scatter and FFT
-  // on s. It does not wait for s: the caller promised the inputs are complete.
+  // CIP_ASYNC | CIP_PIPELINE (resident inputs): the planner beside the previous call's scatter and FFT (PlanPipeline)
   const bool pipelined = (flags & CIP_ASYNC) && (flags & CIP_PIPELINE) && !g_prof.on;
-  hipStream_t ps = s;
-  if (pipelined) {
-    if (!ws->plan_stream) {
-      // the plan streams at the lowest priority: the scatter on s keeps first
-      // call on freed wave slots (C3 pipelined 21.58-21.62 vs 21.46-21.53
-      // Gvis/s at the default priority, 21.15-21.24 at the highest,
-      // profiles/r05v_ab_plan_priority.txt)
-      int prio_lo = 0, prio_hi = 0;
-      CIP_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-      CIP_HIP_CHECK(hipStreamCreateWithPriority(&ws->plan_stream, hipStreamNonBlocking, prio_lo));
-      CIP_HIP_CHECK(hipStreamCreateWithPriority(&ws->plan_stream1, hipStreamNonBlocking, prio_lo));
-      CIP_HIP_CHECK(hipEventCreateWithFlags(&ws->ev_planned, hipEventDisableTiming));
-      CIP_HIP_CHECK(hipEventCreateWithFlags(&ws->ev_entry, hipEventDisableTiming));
-      for (hipEvent_t& e : ws->ev_done) {
-        CIP_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        // the first pipelined calls: the planner starts after the work already on s
-        CIP_HIP_CHECK(hipEventRecord(e, s));
-      }
-    }
-    if (ws->plan_unscoped) {
-      // a planner ran on s since the last pipelined call: its buffers (parity
-      // 0) may still be read there - both plan streams wait for it
-      CIP_HIP_CHECK(hipEventRecord(ws->ev_entry, s));
-      CIP_HIP_CHECK(hipStreamWaitEvent(ws->plan_stream, ws->ev_entry, 0));
-      CIP_HIP_CHECK(hipStreamWaitEvent(ws->plan_stream1, ws->ev_entry, 0));
-      ws->plan_unscoped = false;
-    }
-    ws->parity ^= 1;
-    ps = ws->parity ? ws->plan_stream1 : ws->plan_stream;
-    CIP_HIP_CHECK(hipStreamWaitEvent(ps, ws->ev_done[ws->parity], 0));
-  } else if (ws->parity) {
-    // back to the parity-0 buffers: their last pipelined user may still be queued on s
-    ws->parity = 0;
-  }
-  // the next pipelined call with this parity plans only after everything this
-  // call queued on s - the scatter reads the plan, the FFT the dirty-tile
-  // masks and the weight sum (recorded on every return path)
-  struct DoneMark {
-    Workspace* ws;
-    hipStream_t s;
-    bool armed;
-    ~DoneMark() {
-      if (armed) (void)hipEventRecord(ws->ev_done[ws->parity], s);
-    }
-  } done_mark{ws, s, pipelined};
+  PlanScope plan{ws->pipeline, s};
+  if (const int rc = plan.open(pipelined); rc != CIP_OK) return rc;
   Prepared pp;
-  double* grid = nullptr;
-  ws->parity_scope = pipelined;
-  int rc = prepare(ws, rq, ps, &pp, pipelined ? nullptr : &grid);
-  ws->parity_scope = false;
-  // s continues once the plan exists (also after a failed one, or any early
-  // return: nothing then runs on it)
-  struct PlanJoin {
-    Workspace* ws;
-    hipStream_t ps, s;
-    bool joined;
-    int join() {
-      if (joined) return CIP_OK;
-      joined = true;
-      CIP_HIP_CHECK(hipEventRecord(ws->ev_planned, ps));
-      CIP_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_planned, 0));
-      return CIP_OK;
-    }
-    ~PlanJoin() { (void)join(); }
-  } plan_join{ws, ps, s, !pipelined};
-  if (rc != CIP_OK) (void)plan_join.join();
-  if (grid) {
-    // join the side stream whatever happened (the workspace grid must not be
-    // written by a later call while its memset is still queued)
-    const int jr = join_side(ws, s);
-    if (rc == CIP_OK) rc = jr;
-  }
+  GridUse gu;
+  gu.beside = !pipelined;
+  int rc = prepare(ws, rq, plan.ps, &pp, &gu);
+  // s waits for the plan and the side stream whatever happened (a later call
+  // must not write the workspace grid while its memset is still queued)
+  const int jr = plan.join(), sr = gu.pending ? join_side(ws, s) : CIP_OK;
+  if (rc == CIP_OK) rc = jr != CIP_OK ? jr : sr;
   if (rc != CIP_OK) return rc;
   if (o.params) *o.params = pp.p;
   DirtyStage st;
-  rc = dirty_stage(ws, pp.g, npix_x, npix_y, rq.px, rq.py, s, &st);
-  if (rc != CIP_OK) return rc;
-  // the packed class grids into complex64 planes on the pruned-FFT path (half
-  // the flush and pass-A bytes); CIP_GRID_F32=0 keeps complex128 (A/B)
-  pp.g.grid_f32 = (packed && st.fast && grid_f32_enabled()) ? 1 : 0;
+  if (rc = dirty_stage(ws, pp.g, npix_x, npix_y, rq.px, rq.py, s, &st); rc != CIP_OK) return rc;
+  pp.g.grid_f32 = gu.f32 ? 1 : 0;
   const GridGeometry& g = pp.g;
-  // zeroed beside the planner, or left all-zero by the previous call
-  bool clean = grid != nullptr;
+  double* const grid = gu.grid;
   const int G = pp.plan.group;
-  const int64_t plane_elems = 2 * g.nu * g.nv;
-  const size_t cell_bytes = g.grid_f32 ? sizeof(float) : sizeof(double);  // per real component
-  if (!grid) grid = buf<double>(ws, "grid", plane_elems * G);
-  if (!grid) return CIP_ENOMEM;
-  const size_t group_bytes = cell_bytes * (size_t)plane_elems * (size_t)G;
-  const size_t prev_clean = ws->grid_clean == grid ? ws->grid_clean_bytes : 0;
-  clean = clean || prev_clean >= group_bytes;
-  ws->grid_clean = nullptr;  // dirty until a masked pass A has consumed every written tile
+  const size_t plane_bytes = gu.bytes / (size_t)G;
+  // zeroed beside the planner, or left all-zero by the previous call; dirty
+  // until a masked pass A has consumed every written tile. A larger clean
+  // prefix survives: the call writes only its own group's bytes
+  bool clean = gu.zeroed;
+  const size_t keep = ws->grid_zero.prefix(grid);
+  ws->grid_zero.invalidate();
   const uint32_t* dmask = st.fast ? pp.plan.dmask : nullptr;
   // the plane groups holding planes [plane_lo, plane_hi) (the whole stack
   // unless cip_ms2dirty_wplanes); an empty range leaves a zero image
@@ -371,7 +290,6 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
   if (p_lo >= p_hi) CIP_HIP_CHECK(hipMemsetAsync(dirty_out, 0, sizeof(double) * npix_x * npix_y, s));
   const int64_t rb_stride = (g.mty + 31) / 32;
   const uint32_t* rowbits0 = dmask ? dmask + g.nplanes * (g.mtx * g.mty / 32) : nullptr;
-  if (const int jr = plan_join.join(); jr != CIP_OK) return jr;
   // the packed class's w planes accumulate in a float image (its own
   // precision, one rounding per plane; the final correction writes the fp64
   // image): half the per-plane read-modify-write of pass B. Only beside fp32
@@ -385,39 +303,32 @@ static int ms2dirty_impl(PlanRequest rq, int flags, void* hip_stream, const Dirt
   mode.transposed = st.fast;
   // pipelined calls: leave CU slots to the next call's planner (profiles/r03_ab_scatter_share.txt)
   mode.share_cus = pipelined;
+  PlaneExtras x;
+  x.norm = normalise ? pp.red : nullptr;
+  x.acc_f32 = wacc != nullptr;
   for (int64_t q = p_lo / G; q * G < p_hi; ++q) {
     mode.zeroed = clean;
-    rc = scatter_plane(pp, rq, q, mode, grid, s);
-    if (rc != CIP_OK) return rc;
+    if (rc = scatter_plane(pp, rq, q, mode, grid, s); rc != CIP_OK) return rc;
     for (int64_t p = std::max(q * G, p_lo); p < std::min<int64_t>(q * G + G, p_hi); ++p) {
-      double* plane_p = (double*)((char*)grid + (size_t)(p - q * G) * (size_t)plane_elems * cell_bytes);
-      const uint32_t* dm = dmask ? dmask + p * (g.mtx * g.mty / 32) : nullptr;
-      const uint32_t* rbp = rowbits0 ? rowbits0 + p * rb_stride : nullptr;
-      rc = plane_to_dirty(st, g, p, plane_p, wacc ? (double*)wacc : dirty_out, s, dm, normalise ? pp.red : nullptr,
-                          rbp, p == p_lo, wacc != nullptr);
-      if (rc != CIP_OK) return rc;
+      double* plane_p = (double*)((char*)grid + (size_t)(p - q * G) * plane_bytes);
+      x.dmask = dmask ? dmask + p * (g.mtx * g.mty / 32) : nullptr;
+      x.rowbits = rowbits0 ? rowbits0 + p * rb_stride : nullptr;
+      x.first = p == p_lo;
+      if (rc = plane_to_dirty(st, g, p, plane_p, wacc ? (double*)wacc : dirty_out, s, x); rc != CIP_OK) return rc;
     }
     // a group's planes outside the range were neither written (the scatter
     // skips them) nor read, so a masked pass A still leaves the group clean
     clean = dmask != nullptr;
   }
-  rc = finish_dirty(ws, st, pp.p, g, dirty_out, s, wacc);
-  if (rc != CIP_OK) return rc;
+  if (rc = finish_dirty(ws, st, pp.p, g, dirty_out, s, wacc); rc != CIP_OK) return rc;
   // fused into pass B on the pruned 2-D path; a separate pass otherwise
   if (normalise && (!st.fast || g.do_wstacking))
     CIP_HIP_CHECK(launch_scale_inverse(dirty_out, npix_x * npix_y, pp.red, s));
   if (o.sum_wgt) CIP_HIP_CHECK(hipMemcpyAsync(o.sum_wgt, pp.red, sizeof(double), hipMemcpyDeviceToDevice, s));
-  g_prof.span(5, call.t0, g_prof.mark(s));
-  // CIP_ASYNC: the workspace (grid, planner buffers) is reused by later calls
-  // of this thread in stream order, so nothing on the host waits for it; the
-  // grid-clean mark holds in stream order too
-  if (!(flags & CIP_ASYNC) || g_prof.on) CIP_HIP_CHECK(hipStreamSynchronize(s));
-  else leave_queued(call);
-  if (clean) {
-    ws->grid_clean = grid;
-    ws->grid_clean_bytes = std::max(prev_clean, group_bytes);
-  }
-  g_prof.finish();
+  // CIP_ASYNC: later calls of this thread reuse the workspace (grid, planner buffers) in stream order, so
+  // nothing on the host waits for it; the grid-clean mark holds in stream order too
+  if (rc = end_call(call, !(flags & CIP_ASYNC)); rc != CIP_OK) return rc;
+  if (clean) ws->grid_zero.mark(grid, std::max(keep, gu.bytes));
   return CIP_OK;
 }
 
@@ -433,11 +344,8 @@ int cip_ms2dirty(const double* uvw, int64_t nrow, const double* freq, int64_t nc
                  double* dirty_out, double* sum_wgt_out, cip_gridder_params* params_out) {
   clear_error();
   if (const int rc = public_dtype_check(vis_dtype, wgt_dtype, (flags & CIP_PSF) != 0); rc != CIP_OK) return rc;
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.npix_x = npix_x, rq.npix_y = npix_y, rq.px = pixsize_x, rq.py = pixsize_y;
-  rq.epsilon = epsilon, rq.support = support;
+  const PlanRequest rq = PlanRequest::image(npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support)
+                             .dense(uvw, nrow, freq, nchan, vis, vis_dtype, wgt, wgt_dtype);
   return ms2dirty_impl(rq, flags, hip_stream, {dirty_out, sum_wgt_out, params_out});
 }
 
@@ -450,11 +358,8 @@ int cip_ms2dirty_wplanes(const double* uvw, int64_t nrow, const double* freq, in
   if (!(flags & CIP_WSTACKING)) return set_error(CIP_EINVAL, "a w-plane range needs CIP_WSTACKING");
   if (plane_begin < 0 || plane_end < plane_begin) return set_error(CIP_EINVAL, "invalid w-plane range");
   if (const int rc = public_dtype_check(vis_dtype, wgt_dtype, (flags & CIP_PSF) != 0); rc != CIP_OK) return rc;
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.npix_x = npix_x, rq.npix_y = npix_y, rq.px = pixsize_x, rq.py = pixsize_y;
-  rq.epsilon = epsilon, rq.support = support;
+  PlanRequest rq = PlanRequest::image(npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support)
+                       .dense(uvw, nrow, freq, nchan, vis, vis_dtype, wgt, wgt_dtype);
   rq.plane_begin = plane_begin, rq.plane_end = plane_end;
   return ms2dirty_impl(rq, flags, hip_stream, {dirty_out, sum_wgt_out, params_out});
 }
@@ -466,11 +371,8 @@ int cip_ms2dirty_stokes_i(const double* uvw, int64_t nrow, const double* freq, i
   clear_error();
   if (nrow > 0 && (!wgt4 || (!vis4 && !(flags & CIP_PSF)))) return set_error(CIP_EINVAL, "NULL vis4 or wgt4");
   if (((uintptr_t)flags4 & 3u) != 0u) return set_error(CIP_EINVAL, "flags4 must be 4-byte aligned");
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis4, rq.vis_dtype = CIP_POL4I, rq.wgt = wgt4, rq.wgt_dtype = CIP_POL4I, rq.flags4 = flags4;
-  rq.npix_x = npix_x, rq.npix_y = npix_y, rq.px = pixsize_x, rq.py = pixsize_y;
-  rq.epsilon = epsilon, rq.support = support;
+  const PlanRequest rq = PlanRequest::image(npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support)
+                             .raw(uvw, nrow, freq, nchan, vis4, flags4, wgt4);
   return ms2dirty_impl(rq, flags, hip_stream, {dirty_out, sum_wgt_out, params_out});
 }
 
@@ -480,10 +382,8 @@ int cip_grid_ms(const double* uvw, int64_t nrow, const double* freq, int64_t nch
   clear_error();
   if (nrow < 0) return set_error(CIP_EINVAL, "nrow must be >= 0");
   if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
+  const PlanRequest rq = PlanRequest::fixed(params, pixsize_x, pixsize_y, flags)
+                             .dense(uvw, nrow, freq, nchan, vis, vis_dtype, wgt, wgt_dtype);
   return grid_accumulate(rq, {npix_x, npix_y, flags, grids, sum_wgt}, hip_stream);
 }
 
@@ -495,10 +395,8 @@ int cip_grid_ms_stokes_i(const double* uvw, int64_t nrow, const double* freq, in
   if (nrow < 0) return set_error(CIP_EINVAL, "nrow must be >= 0");
   if (nrow > 0 && (!wgt4 || (!vis4 && !(flags & CIP_PSF)))) return set_error(CIP_EINVAL, "NULL vis4 or wgt4");
   if (((uintptr_t)flags4 & 3u) != 0u) return set_error(CIP_EINVAL, "flags4 must be 4-byte aligned");
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis4, rq.vis_dtype = CIP_POL4I, rq.wgt = wgt4, rq.wgt_dtype = CIP_POL4I, rq.flags4 = flags4;
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
+  const PlanRequest rq =
+      PlanRequest::fixed(params, pixsize_x, pixsize_y, flags).raw(uvw, nrow, freq, nchan, vis4, flags4, wgt4);
   return grid_accumulate(rq, {npix_x, npix_y, flags, grids, sum_wgt}, hip_stream);
 }
 
@@ -510,19 +408,26 @@ static int ragged_args_check(const int32_t* chan_start, const int32_t* chan_stop
   return CIP_OK;
 }
 
+// what stands behind the three, after their own argument checks
+static int grid_tiles(const double* slice_uvw, const RaggedRows& rr, int64_t nslices, const double* freq,
+                      int64_t nchan, const void* vis, int vis_dtype, const void* wgt, int wgt_dtype,
+                      const cip_gridder_params* params, double pixsize_x, double pixsize_y, const GridTarget& t,
+                      void* hip_stream) {
+  if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
+  PlanRequest rq = PlanRequest::fixed(params, pixsize_x, pixsize_y, t.flags)
+                       .dense(slice_uvw, nslices, freq, nchan, vis, vis_dtype, wgt, wgt_dtype);
+  rq.ragged = &rr;
+  return grid_accumulate(rq, t, hip_stream);
+}
+
 int cip_grid_tiles(const double* slice_uvw, const int32_t* chan_start, const int32_t* chan_stop, int64_t nslices,
                    const double* freq, int64_t nchan, const void* vis, int64_t nvis, int vis_dtype, const void* wgt,
                    int wgt_dtype, const cip_gridder_params* params, double pixsize_x, double pixsize_y,
                    int64_t npix_x, int64_t npix_y, int flags, void* hip_stream, double* grids, double* sum_wgt) {
   clear_error();
   if (const int rc = ragged_args_check(chan_start, chan_stop, nslices, nvis); rc != CIP_OK) return rc;
-  if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
-  const RaggedRows rr{chan_start, chan_stop, nvis};
-  PlanRequest rq;
-  rq.uvw = slice_uvw, rq.nrow = nslices, rq.freq = freq, rq.nchan = nchan, rq.ragged = &rr;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
-  return grid_accumulate(rq, {npix_x, npix_y, flags, grids, sum_wgt}, hip_stream);
+  return grid_tiles(slice_uvw, {chan_start, chan_stop, nvis}, nslices, freq, nchan, vis, vis_dtype, wgt, wgt_dtype,
+                    params, pixsize_x, pixsize_y, {npix_x, npix_y, flags, grids, sum_wgt}, hip_stream);
 }
 
 int cip_grid_tiles_strip(const double* slice_uvw, const int32_t* chan_start, const int32_t* chan_stop,
@@ -533,13 +438,8 @@ int cip_grid_tiles_strip(const double* slice_uvw, const int32_t* chan_start, con
   clear_error();
   if (const int rc = ragged_args_check(chan_start, chan_stop, nslices, nvis); rc != CIP_OK) return rc;
   if (nrows < 1) return set_error(CIP_EINVAL, "nrows must be >= 1");
-  if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
-  const RaggedRows rr{chan_start, chan_stop, nvis};
-  PlanRequest rq;
-  rq.uvw = slice_uvw, rq.nrow = nslices, rq.freq = freq, rq.nchan = nchan, rq.ragged = &rr;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
-  return grid_accumulate(rq, {npix_x, npix_y, flags, strip, sum_wgt, row0, nrows}, hip_stream);
+  return grid_tiles(slice_uvw, {chan_start, chan_stop, nvis}, nslices, freq, nchan, vis, vis_dtype, wgt, wgt_dtype,
+                    params, pixsize_x, pixsize_y, {npix_x, npix_y, flags, strip, sum_wgt, row0, nrows}, hip_stream);
 }
 
 int cip_grid_tiles_strip_mask(const double* slice_uvw, const int32_t* chan_start, const int32_t* chan_stop,
@@ -552,13 +452,9 @@ int cip_grid_tiles_strip_mask(const double* slice_uvw, const int32_t* chan_start
   if (const int rc = ragged_args_check(chan_start, chan_stop, nslices, nvis); rc != CIP_OK) return rc;
   if (nrows < 1) return set_error(CIP_EINVAL, "nrows must be >= 1");
   if (!tile_bits) return set_error(CIP_EINVAL, "NULL tile_bits");
-  if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
-  const RaggedRows rr{chan_start, chan_stop, nvis};
-  PlanRequest rq;
-  rq.uvw = slice_uvw, rq.nrow = nslices, rq.freq = freq, rq.nchan = nchan, rq.ragged = &rr;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
-  return grid_accumulate(rq, {npix_x, npix_y, flags, strip, sum_wgt, row0, nrows, tile_bits}, hip_stream);
+  return grid_tiles(slice_uvw, {chan_start, chan_stop, nvis}, nslices, freq, nchan, vis, vis_dtype, wgt, wgt_dtype,
+                    params, pixsize_x, pixsize_y, {npix_x, npix_y, flags, strip, sum_wgt, row0, nrows, tile_bits},
+                    hip_stream);
 }
 
 int cip_grid_to_dirty(double* grids, const cip_gridder_params* params, int64_t npix_x, int64_t npix_y,
@@ -573,11 +469,9 @@ int cip_grid_to_dirty(double* grids, const cip_gridder_params* params, int64_t n
   int rc = dirty_stage(ws, g, npix_x, npix_y, pixsize_x, pixsize_y, s, &st);
   if (rc != CIP_OK) return rc;
   for (int64_t p = 0; p < g.nplanes; ++p) {
-    rc = plane_to_dirty(st, g, p, grids + p * 2 * g.nu * g.nv, dirty_out, s);
-    if (rc != CIP_OK) return rc;
+    if (rc = plane_to_dirty(st, g, p, grids + p * 2 * g.nu * g.nv, dirty_out, s); rc != CIP_OK) return rc;
   }
-  rc = finish_dirty(ws, st, *params, g, dirty_out, s);
-  if (rc != CIP_OK) return rc;
+  if (rc = finish_dirty(ws, st, *params, g, dirty_out, s); rc != CIP_OK) return rc;
   return end_call(call);
 }
 
@@ -591,19 +485,13 @@ int cip_grid_plane(const double* uvw, int64_t nrow, const double* freq, int64_t 
   if (plane < 0 || plane >= params->nplanes) return set_error(CIP_EINVAL, "plane out of range");
   if (!public_dtypes(vis_dtype, wgt_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
   CIP_BEGIN_CALL(hip_stream, true)
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = vis, rq.vis_dtype = vis_dtype, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.npix_x = rq.npix_y = 2;  // a dummy image size, as in grid_accumulate
-  rq.px = pixsize_x, rq.py = pixsize_y, rq.given = params;
-  rq.support = params->support, rq.do_wstacking = params->do_wstacking;
-  rq.packed = (flags & CIP_ACC_SINGLE) != 0;
+  PlanRequest rq = PlanRequest::fixed(params, pixsize_x, pixsize_y, flags)
+                       .dense(uvw, nrow, freq, nchan, vis, vis_dtype, wgt, wgt_dtype);
   rq.want_group = false;  // one plane per work unit: `plane` indexes the plan's ranges
   Prepared pp;
   int rc = prepare(ws, rq, s, &pp);
   if (rc != CIP_OK) return rc;
-  rc = scatter_plane(pp, rq, plane, ScatterMode(), grid_out, s);
-  if (rc != CIP_OK) return rc;
+  if (rc = scatter_plane(pp, rq, plane, ScatterMode(), grid_out, s); rc != CIP_OK) return rc;
   return end_call(call);
 }
 

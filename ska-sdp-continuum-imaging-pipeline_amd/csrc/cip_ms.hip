@@ -182,7 +182,6 @@ int convolve_impl(const double* in, int64_t nx, int64_t ny, const double* taps, 
       rc != CIP_OK)
     return rc;
   CIP_HIP_CHECK(launch_convolve(in, nx, ny, (int)R, dtaps, tmp, out, s));
-  leave_queued(call);
   return CIP_OK;
 }
 

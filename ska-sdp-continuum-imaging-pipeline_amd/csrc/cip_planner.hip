@@ -198,12 +198,12 @@ static int make_plan(Workspace* ws, const double* uvw, const double* fx, const R
   return CIP_OK;
 }
 
-int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, double** grid_out) {
+int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, GridUse* grid_out) {
   const int64_t nrow = rq.nrow, nchan = rq.nchan;
   const int vis_dtype = rq.vis_dtype;
   const bool packed = rq.packed;
   const RaggedRows* ragged = rq.ragged;
-  if (!ws->parity_scope) ws->plan_unscoped = true;
+  ws->pipeline.planner_starts();
   if (!vis_dtype_ok(vis_dtype)) return set_error(CIP_EINVAL, "vis dtype must be complex64 or complex128");
   if (!wgt_dtype_ok(rq.wgt_dtype)) return set_error(CIP_EINVAL, "wgt dtype must be float32, float64 or none");
   const int wgt_dtype = rq.wgt == nullptr ? CIP_NONE : rq.wgt_dtype;
@@ -341,19 +341,19 @@ int prepare(Workspace* ws, const PlanRequest& rq, hipStream_t s, Prepared* out, 
   out->red = red;
   const int group = rq.want_group ? wstack_group(out->g, packed) : 1;
   if (grid_out) {
-    // the grid is known now: zero its first plane group beside the planner
-    // (complex64 cells for the packed class on the pruned-FFT path, as
-    // ms2dirty_impl lays them out)
-    const int64_t gplanes = group;
-    const bool f32 = packed && grid_is_transposed(out->g, rq.npix_x, rq.npix_y) && grid_f32_enabled();
-    const size_t gbytes = (f32 ? sizeof(float) : sizeof(double)) * 2 * out->g.nu * out->g.nv * gplanes;
-    double* grid = buf<double>(ws, "grid", 2 * out->g.nu * out->g.nv * gplanes);
-    if (!grid) return CIP_ENOMEM;
-    if (ws->grid_clean != grid || ws->grid_clean_bytes < gbytes) {
-      const int zr = zero_on_side(ws, grid, gbytes, s);
-      if (zr != CIP_OK) return zr;
+    // the grid is known now: its first plane group (sized for complex128 cells
+    // whatever the cell type), zeroed beside the planner unless left clean
+    GridUse& u = *grid_out;
+    const size_t cells = (size_t)(2 * out->g.nu * out->g.nv) * (size_t)group;
+    u.f32 = grid_planes_f32(packed, out->g, rq.npix_x, rq.npix_y);
+    u.bytes = (u.f32 ? sizeof(float) : sizeof(double)) * cells;
+    u.grid = grid_buffer(ws, sizeof(double) * cells);
+    if (!u.grid) return CIP_ENOMEM;
+    u.zeroed = ws->grid_zero.covers(u.grid, u.bytes);
+    if (!u.zeroed && u.beside) {
+      if (const int zr = zero_on_side(ws, u.grid, u.bytes, s); zr != CIP_OK) return zr;
+      u.zeroed = u.pending = true;
     }
-    *grid_out = grid;
   }
   hipEvent_t e_prep = g_prof.mark(s);
   g_prof.span(0, g_prof.pool.empty() ? nullptr : g_prof.pool[0], e_prep);

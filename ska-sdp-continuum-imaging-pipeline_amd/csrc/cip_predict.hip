@@ -1,18 +1,21 @@
-// cip_predict.hip - the predict (degridding) driver: dirty2ms_impl and cip_dirty2ms.
+// cip_predict.hip - the predict (degridding) driver: cip_dirty2ms.
 #include <algorithm>
 #include <cmath>
 
 #include "cip_host.h"
 
-namespace cip {
+using namespace cip;
 
-// Predict (cip_dirty2ms): the transpose of ms2dirty_impl's pipeline, run
-// backwards - prepare the image, zero-pad it into grid planes, forward FFT,
-// degrid through the scatter's tile plan.
-static int dirty2ms_impl(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const double* dirty,
-                         int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y, double epsilon,
-                         int support, int flags, const void* wgt, int wgt_dtype, void* hip_stream, void* vis_io,
-                         int vis_dtype, cip_gridder_params* params_out) {
+extern "C" {
+
+// Predict: the transpose of ms2dirty_impl's pipeline, run backwards - prepare
+// the image, zero-pad it into grid planes, forward FFT, degrid through the
+// scatter's tile plan.
+int cip_dirty2ms(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const double* dirty,
+                 int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y, double epsilon, int support,
+                 int flags, const void* wgt, int wgt_dtype, void* hip_stream, void* vis_io, int vis_dtype,
+                 cip_gridder_params* params_out) {
+  clear_error();
   if (flags & CIP_ACC_SINGLE)
     return set_error(CIP_EINVAL, "cip_dirty2ms: CIP_ACC_SINGLE is not supported (the degridder is fp64)");
   if (flags & CIP_PSF) return set_error(CIP_EINVAL, "cip_dirty2ms: CIP_PSF has no meaning for a predict");
@@ -35,15 +38,13 @@ static int dirty2ms_impl(const double* uvw, int64_t nrow, const double* freq, in
     return rc;
   }
   CIP_BEGIN_CALL(hip_stream, true)
-  ws->parity = 0;
+  ws->pipeline.rewind();
   // the invert's planner on unit visibilities (vis == NULL, as a PSF call): the
   // same placement, tiles and work units, and the same CIP_REUSE_PLAN key as a
   // fp64-class cip_ms2dirty of this geometry
-  PlanRequest rq;
-  rq.uvw = uvw, rq.nrow = nrow, rq.freq = freq, rq.nchan = nchan;
-  rq.vis = nullptr, rq.vis_dtype = CIP_C64, rq.wgt = wgt, rq.wgt_dtype = wgt_dtype;
-  rq.npix_x = npix_x, rq.npix_y = npix_y, rq.px = pixsize_x, rq.py = pixsize_y;
-  rq.epsilon = epsilon, rq.support = support, rq.do_wstacking = do_wstacking;
+  PlanRequest rq = PlanRequest::image(npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support)
+                       .dense(uvw, nrow, freq, nchan, nullptr, CIP_C64, wgt, wgt_dtype);
+  rq.do_wstacking = do_wstacking;
   rq.reuse = (flags & CIP_REUSE_PLAN) != 0;
   Prepared pp;
   int rc = prepare(ws, rq, s, &pp);
@@ -63,9 +64,9 @@ static int dirty2ms_impl(const double* uvw, int64_t nrow, const double* freq, in
   const int64_t plane_cells = g.nu * g.nv;
   // the invert's grid buffer, borrowed: it holds dense FFT output afterwards,
   // so the invert's all-zero promise about it ends here
-  CIP_ALLOC(planes, double, "grid", 2 * plane_cells * G)
-  ws->grid_clean = nullptr;
-  ws->grid_clean_bytes = 0;
+  double* planes = grid_buffer(ws, sizeof(double) * (size_t)(2 * plane_cells * G));
+  if (!planes) return CIP_ENOMEM;
+  ws->grid_zero.invalidate();
   CIP_ALLOC(image, double, "degrid_image", npix_x * npix_y)
   const int64_t nvis = pp.m.nvis;
   DegridOut o;
@@ -123,21 +124,6 @@ static int dirty2ms_impl(const double* uvw, int64_t nrow, const double* freq, in
     g_prof.span(2, a, g_prof.mark(s));
   }
   return end_call(call);
-}
-
-}  // namespace cip
-
-using namespace cip;
-
-extern "C" {
-
-int cip_dirty2ms(const double* uvw, int64_t nrow, const double* freq, int64_t nchan, const double* dirty,
-                 int64_t npix_x, int64_t npix_y, double pixsize_x, double pixsize_y, double epsilon, int support,
-                 int flags, const void* wgt, int wgt_dtype, void* hip_stream, void* vis_io, int vis_dtype,
-                 cip_gridder_params* params_out) {
-  clear_error();
-  return dirty2ms_impl(uvw, nrow, freq, nchan, dirty, npix_x, npix_y, pixsize_x, pixsize_y, epsilon, support, flags,
-                       wgt, wgt_dtype, hip_stream, vis_io, vis_dtype, params_out);
 }
 
 }  // extern "C"

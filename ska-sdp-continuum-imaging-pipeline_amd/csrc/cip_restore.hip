@@ -362,7 +362,7 @@ int beam_fit_impl(const double* psf, int64_t px, int64_t py, int64_t cx, int64_t
                                  psf + i_lo * py + j_lo, sizeof(double) * (size_t)py,
                                  sizeof(double) * (size_t)(j_hi - j_lo), (size_t)(i_hi - i_lo), hipMemcpyDeviceToHost,
                                  s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  if (const int rc = end_call(call); rc != CIP_OK) return rc;
   return fit_window_impl(who, win, r, cut, out);
 }
 
@@ -424,7 +424,6 @@ int restore_impl(const double* model, const double* residual, int64_t nx, int64_
       rc != CIP_OK)
     return rc;
   CIP_HIP_CHECK(launch_restore(model, residual, out, nx, ny, (int)R, taps, rows, s));
-  leave_queued(call);
   return CIP_OK;
 }
 

@@ -231,7 +231,7 @@ int cip_tile_runs(const double* uvw, int64_t nrow, const double* freq, int64_t n
   if (!run_row || !run_c0 || !run_c1) return set_error(CIP_EINVAL, "NULL output buffer");
   CIP_HIP_CHECK(launch_tile_run_emit(uvw, nrow, winv, nchan, tile_size3[0], tile_size3[1], tile_size3[2],
                                      row_offset, row_runs, run_key, run_row, run_c0, run_c1, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
+  if (const int rc = end_call(call); rc != CIP_OK) return rc;
   *n_runs = total;
   return CIP_OK;
 }
@@ -289,8 +289,7 @@ int cip_facet_rephase(const double* uvw, int64_t nrow, const double* freq, int64
     for (int b = 0; b < 3; ++b) qt[3 * a + b] = Q[3 * b + a];
   CIP_HIP_CHECK(launch_facet_rephase(uvw, nrow, freq, nchan, vis_out ? vis : nullptr, vis_dtype == CIP_C128, qt, l0, m0,
                                      uvw_out, delay, vis_out, s));
-  CIP_HIP_CHECK(hipStreamSynchronize(s));
-  return CIP_OK;
+  return end_call(call);
 }
 
 }  // extern "C"

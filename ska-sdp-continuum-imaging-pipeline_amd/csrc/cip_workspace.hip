@@ -21,13 +21,6 @@ void clear_error() { g_last_error.clear(); }
 
 thread_local Profiler g_prof;
 
-static int settle_async(Workspace* ws, hipStream_t s) {
-  hipStream_t prev = ws->async_stream;
-  ws->async_stream = nullptr;
-  if (prev && prev != s) CIP_HIP_CHECK(hipStreamSynchronize(prev));
-  return CIP_OK;
-}
-
 // Zero `bytes` at `p` on the workspace's side stream, ordered after the work
 // already queued on s; join_side() makes s wait for it.
 int zero_on_side(Workspace* ws, void* p, size_t bytes, hipStream_t s) {
@@ -40,15 +33,79 @@ int zero_on_side(Workspace* ws, void* p, size_t bytes, hipStream_t s) {
   CIP_HIP_CHECK(hipStreamWaitEvent(ws->side, ws->ev_fork, 0));
   CIP_HIP_CHECK(hipMemsetAsync(p, 0, bytes, ws->side));
   CIP_HIP_CHECK(hipEventRecord(ws->ev_join, ws->side));
-  ws->side_pending = true;
   return CIP_OK;
 }
 
 int join_side(Workspace* ws, hipStream_t s) {
-  if (!ws->side_pending) return CIP_OK;
-  ws->side_pending = false;
+  if (!ws->ev_join) return CIP_OK;  // no zero_on_side yet
   CIP_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_join, 0));
   return CIP_OK;
+}
+
+int PlanScope::open(bool pipelined) {
+  if (!pipelined) {
+    // back to the parity-0 buffers: their last pipelined user may still be queued on s
+    pl.parity = 0;
+    return CIP_OK;
+  }
+  if (!pl.plan_stream) {
+    // the plan streams at the lowest priority: the scatter on s keeps first
+    // call on freed wave slots (C3 pipelined 21.58-21.62 vs 21.46-21.53
+    // Gvis/s at the default priority, 21.15-21.24 at the highest,
+    // profiles/r05v_ab_plan_priority.txt)
+    int prio_lo = 0, prio_hi = 0;
+    CIP_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    CIP_HIP_CHECK(hipStreamCreateWithPriority(&pl.plan_stream, hipStreamNonBlocking, prio_lo));
+    CIP_HIP_CHECK(hipStreamCreateWithPriority(&pl.plan_stream1, hipStreamNonBlocking, prio_lo));
+    CIP_HIP_CHECK(hipEventCreateWithFlags(&pl.ev_planned, hipEventDisableTiming));
+    CIP_HIP_CHECK(hipEventCreateWithFlags(&pl.ev_entry, hipEventDisableTiming));
+    for (hipEvent_t& e : pl.ev_done) {
+      CIP_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      // the first pipelined calls: the planner starts after the work already on s
+      CIP_HIP_CHECK(hipEventRecord(e, s));
+    }
+  }
+  if (pl.plan_unscoped) {
+    // a planner ran on s since the last pipelined call: its buffers (parity
+    // 0) may still be read there - both plan streams wait for it
+    CIP_HIP_CHECK(hipEventRecord(pl.ev_entry, s));
+    CIP_HIP_CHECK(hipStreamWaitEvent(pl.plan_stream, pl.ev_entry, 0));
+    CIP_HIP_CHECK(hipStreamWaitEvent(pl.plan_stream1, pl.ev_entry, 0));
+    pl.plan_unscoped = false;
+  }
+  // this parity's planner buffers: after their last user, the call before the
+  // previous one. Not after s: the caller promised the inputs are complete
+  pl.parity ^= 1;
+  ps = pl.parity ? pl.plan_stream1 : pl.plan_stream;
+  CIP_HIP_CHECK(hipStreamWaitEvent(ps, pl.ev_done[pl.parity], 0));
+  pl.parity_scope = armed = true;
+  joined = false;
+  return CIP_OK;
+}
+
+int PlanScope::join() {
+  if (joined) return CIP_OK;
+  joined = true;
+  pl.parity_scope = false;
+  CIP_HIP_CHECK(hipEventRecord(pl.ev_planned, ps));
+  CIP_HIP_CHECK(hipStreamWaitEvent(s, pl.ev_planned, 0));
+  return CIP_OK;
+}
+
+PlanScope::~PlanScope() {
+  (void)join();
+  if (armed) (void)hipEventRecord(pl.ev_done[pl.parity], s);
+}
+
+void PlanPipeline::destroy() {
+  for (hipStream_t st : {plan_stream, plan_stream1})
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+    }
+  for (hipEvent_t e : {ev_done[0], ev_done[1], ev_planned, ev_entry})
+    if (e) (void)hipEventDestroy(e);
+  *this = PlanPipeline();
 }
 
 static std::mutex g_ws_mutex;
@@ -73,9 +130,8 @@ static void destroy_workspace(Workspace* ws) {
   int prev_dev = -1;
   (void)hipGetDevice(&prev_dev);
   if (prev_dev != ws->device) (void)hipSetDevice(ws->device);
-  if (ws->async_stream) (void)hipStreamSynchronize(ws->async_stream);
-  if (ws->plan_stream) (void)hipStreamSynchronize(ws->plan_stream);
-  if (ws->plan_stream1) (void)hipStreamSynchronize(ws->plan_stream1);
+  if (ws->async_queued) (void)hipStreamSynchronize(ws->async_stream);
+  ws->pipeline.destroy();
   for (auto& kv : ws->bufs)
     if (kv.second.ptr) (void)hipFree(kv.second.ptr);
   for (auto& p : ws->plans) (void)hipfftDestroy(p.h);
@@ -90,15 +146,6 @@ static void destroy_workspace(Workspace* ws) {
   }
   if (ws->ev_fork) (void)hipEventDestroy(ws->ev_fork);
   if (ws->ev_join) (void)hipEventDestroy(ws->ev_join);
-  for (hipStream_t ps : {ws->plan_stream, ws->plan_stream1})
-    if (ps) {
-      (void)hipStreamSynchronize(ps);
-      (void)hipStreamDestroy(ps);
-    }
-  for (hipEvent_t e : ws->ev_done)
-    if (e) (void)hipEventDestroy(e);
-  if (ws->ev_planned) (void)hipEventDestroy(ws->ev_planned);
-  if (ws->ev_entry) (void)hipEventDestroy(ws->ev_entry);
   const int dev = ws->device;
   delete ws;
   if (prev_dev >= 0 && prev_dev != dev) (void)hipSetDevice(prev_dev);
@@ -133,21 +180,16 @@ static Workspace* workspace() {
   g_reaper.armed = true;
   std::lock_guard<std::mutex> lock(g_ws_mutex);
   auto it = g_ws.find(key);
-  if (it != g_ws.end()) {
-    ++it->second->call_seq;  // every entry point takes its workspace once per call
-    return it->second;
-  }
+  if (it != g_ws.end()) return it->second;
   Workspace* ws = new Workspace();
   ws->device = dev;
   g_ws[key] = ws;
   return ws;
 }
 
-// grow-only device buffer; returns nullptr (and sets the error) on failure
-void* buf_bytes(Workspace* ws, const char* name, size_t bytes) {
-  DevBuf& b = ws->bufs[(ws->parity_scope && ws->parity) ? std::string(name) + "~1" : std::string(name)];
+static void* buf_named(Workspace* ws, const std::string& name, size_t bytes) {
+  DevBuf& b = ws->bufs[name];
   if (b.bytes < bytes) {
-    if (b.ptr && b.ptr == (void*)ws->grid_clean) ws->grid_clean = nullptr;  // a new buffer is not known zero
     if (b.ptr) ws->saved_valid = false;  // the saved plan may point into it
     if (b.ptr) (void)hipFree(b.ptr);
     b.ptr = nullptr;
@@ -156,12 +198,21 @@ void* buf_bytes(Workspace* ws, const char* name, size_t bytes) {
     const size_t want = bytes + bytes / 8;
     if (hipMalloc(&b.ptr, want) != hipSuccess) {
       (void)hipGetLastError();
-      set_error(CIP_ENOMEM, std::string("hipMalloc failed for workspace buffer ") + name);
+      set_error(CIP_ENOMEM, "hipMalloc failed for workspace buffer " + name);
       return nullptr;
     }
     b.bytes = want;
   }
   return b.ptr;
+}
+
+void* buf_bytes(Workspace* ws, const char* name, size_t bytes) {
+  return buf_named(ws, ws->pipeline.odd_names() ? std::string(name) + "~1" : std::string(name), bytes);
+}
+
+double* grid_buffer(Workspace* ws, size_t bytes) {
+  if (ws->bufs["grid"].bytes < bytes) ws->grid_zero.invalidate();  // buf_named reallocates: not known zero
+  return (double*)buf_named(ws, "grid", bytes);
 }
 
 // grow-only pinned host memory (the readback staging and each table's own)
@@ -259,9 +310,12 @@ int fft_twiddles(Workspace* ws, int64_t n, hipStream_t s, double** out) {
 int begin_call(void* hip_stream, bool profiled, Call* c) {
   g_last_error.clear();
   c->s = (hipStream_t)hip_stream;
-  c->ws = workspace();
-  if (!c->ws) return set_error(CIP_EHIP, "no HIP device");
-  if (const int sr = settle_async(c->ws, c->s); sr != CIP_OK) return sr;
+  Workspace* ws = workspace();
+  if (!ws) return set_error(CIP_EHIP, "no HIP device");
+  // an earlier call's work queued on another stream (NULL is a stream too: the default one)
+  if (ws->async_queued && ws->async_stream != c->s) CIP_HIP_CHECK(hipStreamSynchronize(ws->async_stream));
+  ws->async_queued = false;
+  c->ws = ws;  // from here ~Call notes the stream
   c->profiled = profiled;
   if (profiled) {
     g_prof.reset();
@@ -270,14 +324,18 @@ int begin_call(void* hip_stream, bool profiled, Call* c) {
   return CIP_OK;
 }
 
-int end_call(const Call& c) {
+int end_call(Call& c, bool wait) {
   if (c.profiled) g_prof.span(5, c.t0, g_prof.mark(c.s));
+  if (!wait && !(c.profiled && g_prof.on)) return CIP_OK;  // queued: ~Call notes the stream
   CIP_HIP_CHECK(hipStreamSynchronize(c.s));
+  c.synced = true;
   if (c.profiled) g_prof.finish();
   return CIP_OK;
 }
 
-void leave_queued(const Call& c) { c.ws->async_stream = c.s; }
+Call::~Call() {
+  if (ws && !synced) ws->async_queued = true, ws->async_stream = s;
+}
 
 }  // namespace cip
 
